@@ -2,6 +2,12 @@
 """Benchmark: env-steps/sec (batched episodes) on ER-200 MaxCut (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|rollout] [--envs B] [--n N]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds the measurements that take
+runs of their own (env_step_roofline, untimed_per_episode_costs, learn_loop, the CPU baselines).  --dump-outputs
+DIR writes what the last timed step computed (actions, rewards, dones, observations, losses, parameters) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared array for array.
 
 Default workload = BASELINE.json configs[2]: ER_200spin, 8192 parallel episodes per
 GPU (each on its own graph), the FULL ECO-DQN train loop:
@@ -20,9 +26,9 @@ Prints ONE JSON line on rank 0 with
             per graph, backward = 2F; peak = the dense peak of the MFMA dtype the kernel ISSUES
             (f16 / bf16, 2.5 PFLOP/s: the fp16x2 split kernels; bf16x3 in the per-episode N > 512 one), frac <= 1 by construction;
             the f32-MFMA figure (157.3) is kept as a separately named field.
-  env_step_roofline: the env step kernel alone (same B, N), SURVEY.md 8d incremental algorithmic bytes
-            per env-step (N + 14.25 N + 28 N) x rate / HBM peak (8 TB/s).
-  cpu_baseline: the oracle ('port') env + torch-CPU MPNN act loop on this host.
+  env_step_roofline (--full): the env step kernel alone (same B, N), SURVEY.md 8d incremental algorithmic
+            bytes per env-step (N + 14.25 N + 28 N) x rate / HBM peak (8 TB/s).
+  cpu_baseline (--full): the oracle ('port') env + torch-CPU MPNN act loop on this host.
 """
 import argparse
 import json
@@ -520,6 +526,8 @@ def dry_run_bench(args, world, rank, local):
         tdist.barrier()
     dt = time.perf_counter() - t0
     per_rank = _gather_floats([dt, float(local)], world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sum": np.array([x.sum()])})
     if rank == 0:
         print(json.dumps({"metric": "dry-run (launcher check)", "value": 0.0, "unit": "steps/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -613,6 +621,32 @@ def build_train_agent(dev, B, n, graph="ER", gparam=0.15, minibatch=2048, seed=1
     return agent, store, env, lr
 
 
+DUMP_ARRAY_BYTES = 7 << 20  # per array; every workload dumps at most 8 arrays (under 64 MB with the row indices)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each named tensor / array as dirname/<name>.npy (float64 stays float64, integers
+    become float64, everything else float32).  An array above DUMP_ARRAY_BYTES is cut to a fixed sample of its
+    rows (dimension 0; sorted indices drawn without replacement from numpy's default_rng(0), so two builds dump
+    the same rows); <name>.rows.npy then holds the sampled row indices."""
+    assert len(arrays) <= 8
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        t = a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+        if t.dim() == 0:
+            t = t.reshape(1)
+        to = torch.float64 if t.dtype == torch.float64 or not t.dtype.is_floating_point else torch.float32
+        row_bytes = max(1, t[0].numel()) * (8 if to == torch.float64 else 4)
+        if t.shape[0] * row_bytes > DUMP_ARRAY_BYTES:
+            k = max(1, DUMP_ARRAY_BYTES // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], k, replace=False))
+            t = t[torch.as_tensor(rows, device=t.device)]
+            np.save(os.path.join(dirname, name + ".rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), t.to(to).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -636,7 +670,14 @@ def main():
     ap.add_argument("--target", default="CUT",
                     choices=["CUT", "MIN_COVER", "MIN_CUT", "MAX_IND_SET", "MAX_CLIQUE", "MIN_DOM_SET"],
                     help="envstep: OptimisationTarget (set problems use MAIN_OBSERVABLES and unit weights)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the untimed "
+                         "per-episode costs, DQN.learn() end to end, the env step kernel's roofline, the CPU "
+                         "baselines, and (er20) the forward's roofline from an eager episode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64; large arrays as a fixed seeded sample of their rows)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -703,9 +744,17 @@ def main():
     from eco_hip.parallel import max_over_ranks
     dt = max_over_ranks(dt_rank, device=dev)
     pg = process_group_info(world, dt_rank, args.steps, local, dev)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left for its caller: the actions it took, the env's rewards / dones / next
+        # observations, the gradient steps' losses and the two networks' parameters after them
+        k = agent._k_per_vec if train and agent._ready else 0
+        dump_outputs(args.dump_outputs, {
+            "actions": agent._actions, "rewards": env.rewards, "dones": env.dones, "obs": env.obs_x,
+            "losses": agent._loss_buf[agent._loss_n - k:agent._loss_n] if k else None,
+            "params": agent.network.flat, "target_params": agent.target_network.flat})
 
     fixed = loop = None
-    if train:
+    if train and args.full:
         test = make_test_env(agent, dev, graph=args.graph, gparam=gparam)
         fixed = untimed_costs(agent, B, world, dev, test)
         loop = learn_loop(agent, B, world, dev, test)
@@ -759,10 +808,11 @@ def main():
             "kernels_ms_per_step": {k: v[0] / args.steps for k, v in kern.items()},
             "process_group": pg,
         }
-        # the env step kernel alone on this bench's graphs: SURVEY.md 8d's HBM roofline of the env step
-        es_rate, es_ms = envstep_rate(dev, B, n, store=store)
-        out["env_step_roofline"] = envstep_roofline(es_rate, es_ms, n, B)
-        out["untimed_per_episode_costs"] = fixed
+        if args.full:
+            # the env step kernel alone on this bench's graphs: SURVEY.md 8d's HBM roofline of the env step
+            es_rate, es_ms = envstep_rate(dev, B, n, store=store)
+            out["env_step_roofline"] = envstep_roofline(es_rate, es_ms, n, B)
+            out["untimed_per_episode_costs"] = fixed
         if loop is not None:
             loop["ratio_to_headline"] = loop["value"] / value
             out["learn_loop"] = loop
@@ -772,7 +822,7 @@ def main():
             out["roofline"].update(mfma_busy=mf["mfma_busy"], issued_f16_tflops=issued,
                                    f16_peak=F16_MFMA_PEAK_TFLOPS, f16_frac=issued / F16_MFMA_PEAK_TFLOPS,
                                    mfma_source=mf["source"])
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline_learn_loop"] = cpu_baseline(n, train=train)
             if args.graph == "ER":
                 out["cpu_baseline"] = cpu_refcost_baseline(n, gpus_on_node=torch.cuda.device_count())
@@ -889,7 +939,10 @@ def inference_bench(args, world, rank, local, dev, dist):
     dt_rank = time.perf_counter() - t0
     dt = max_over_ranks(dt_rank, device=dev)
     pg = process_group_info(world, dt_rank, args.steps, local, dev)
-    if graphed:  # the forward launches of one eager episode, timed with HIP events on the launch stream
+    if args.dump_outputs and rank == 0:  # the last timed step's greedy actions and what the env returned for them
+        dump_outputs(args.dump_outputs, {"actions": acts, "rewards": env.rewards, "dones": env.dones,
+                                         "obs": env.obs_x, "best_cut": env.read()["best_solution"]})
+    if graphed and args.full:  # the forward launches of one eager episode, timed with HIP events on the launch stream
         net.timer = timers
         t_ep[0] = T
         for _ in range(T):
@@ -920,11 +973,12 @@ def inference_bench(args, world, rank, local, dev, dist):
                                    f"({'configs[4]' if args.workload == 'gset' else 'configs[1]'})",
                        "n_spins": n, "envs_per_gpu": B, "graphs": ngraphs, "max_steps": T,
                        "parallelism": f"episodes sharded, dp{world}, no collective until the best-cut reduce"},
+            # no forward launch was timed when whole episodes replay a HIP graph: the eager episode needs --full
             "roofline": dict(mfma_roofline(fl / (fwd_ms * 1e-3) / 1e12, forward_kernel_name(n, kind, ngraphs)),
                              traffic=None, avg_launch_ms=fwd_ms, flops_per_launch=fl,
                              timing=("HIP events around the forward launches of one eager episode after the timed "
                                      "region (the timed episodes replay a HIP graph)" if graphed else
-                                     "HIP events around every forward launch of the timed region")),
+                                     "HIP events around every forward launch of the timed region")) if timers else None,
             "execution": ("whole episodes (T steps: forward + fused greedy act + env step) replayed from one HIP "
                           "graph; the episodes are reset on their graphs every T steps inside the timed region"
                           if graphed else "eager launches"),
@@ -1003,6 +1057,8 @@ def envstep_bench(args, world, rank, local, dev, dist):
     dt = max_over_ranks(dt_rank, device=dev)
     pg = process_group_info(world, dt_rank, steps, local, dev)
     env.check_errors()
+    if args.dump_outputs and rank == 0:  # what the last replayed env step returned
+        dump_outputs(args.dump_outputs, {"rewards": env.rewards, "dones": env.dones, "obs": env.obs_x})
     k_ms = e0.elapsed_time(e1) / steps
     nnz = float(np.diff(store.row_ptr.cpu().numpy(), axis=1).sum(axis=1).mean())
     W = _lib.obs_x_stride(len(obs))

@@ -13,10 +13,10 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 "$OUT/smoke.log"
 for w in train er20 gset ba500; do
   case $w in
-    train) args="";;
-    er20) args="--workload er20 --steps 40 --warmup 5";;
+    train) args="--full";;
+    er20) args="--workload er20 --steps 40 --warmup 5 --full";;
     gset) args="--workload gset --steps 20 --warmup 3";;
-    ba500) args="--graph BA --n 500 --steps 4 --warmup 2 --no-cpu-baseline";;
+    ba500) args="--graph BA --n 500 --steps 4 --warmup 2 --full --no-cpu-baseline";;
   esac
   timeout -k 10 400 python -u bench.py $args > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -5 "$OUT/bench_$w.err"; exit 5; }
   python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['value']), round(d['ms_per_step'],4), d.get('launch','')[:20], round(d['roofline']['frac'],4))" "$OUT/bench_$w.json" $w

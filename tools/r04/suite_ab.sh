@@ -15,7 +15,7 @@ for rep in 1 2; do
   i=0
   for lib in "$@"; do
     if [ "$lib" != default ]; then export ECO_HIP_LIB=$ROOT/$lib; else unset ECO_HIP_LIB; fi
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > "$OUT/b${rep}_v$i.json" 2> "$OUT/b${rep}_v$i.err" || { tail -5 "$OUT/b${rep}_v$i.err"; exit 5; }
+    timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > "$OUT/b${rep}_v$i.json" 2> "$OUT/b${rep}_v$i.err" || { tail -5 "$OUT/b${rep}_v$i.err"; exit 5; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['value']), round(d['ms_per_step'],3), {k: round(v,3) for k,v in d['kernels_ms_per_step'].items()}, round(d['roofline']['avg_launch_ms'],4), d.get('untimed_per_episode_costs',{}).get('evaluate_agent_ms'))" "$OUT/b${rep}_v$i.json" "$lib"
     i=$((i+1))
   done
