@@ -45,6 +45,11 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_d(double v) {  // fixed butterfly order: every lane gets the same bits
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 __device__ __forceinline__ float wave_sum_f(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -59,7 +64,7 @@ __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfi
 
 // ---- per-episode scalar record of the batched env ----
 struct alignas(16) EpScal {
-  double score;          // SpinSystemBase.score (quality = cut + |lb|), exact integer
+  double score;          // SpinSystemBase.score (quality = cut + |lb|), exact integer (integer weights)
   double nscore;         // normalized_score, f64 running sum (spinsystem.py:400)
   double best_score;
   double best_nscore;
@@ -91,7 +96,8 @@ struct EnvLayout {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-inline EnvLayout env_layout(int N, int T, int B) {
+// float_weights: the resident local field is f64 (float-weighted graph sets); 0 keeps the integer layout byte for byte
+inline EnvLayout env_layout(int N, int T, int B, int float_weights = 0) {
   EnvLayout L;
   L.N = N; L.T = T; L.B = B;
   L.words = (N + 63) / 64;
@@ -103,7 +109,7 @@ inline EnvLayout env_layout(int N, int T, int B) {
   L.off_tab = o;     o = align_up(o + 256 + sizeof(double) * (size_t)(T + 1), 256);
   L.off_scal = o;    o = align_up(o + sizeof(EpScal) * (size_t)B, 256);
   L.off_spins = o;   o = align_up(o + (size_t)B * N, 256);
-  L.off_field = o;   o = align_up(o + (size_t)B * N * 4, 256);
+  L.off_field = o;   o = align_up(o + (size_t)B * N * (float_weights ? 8 : 4), 256);
   L.off_tsf = o;     o = align_up(o + (size_t)B * N * 2, 256);
   L.off_best = o;    o = align_up(o + (size_t)B * N, 256);
   L.off_vidx = o;    o = align_up(o + (size_t)B * cap * 4, 256);

@@ -117,6 +117,77 @@ __global__ __launch_bounds__(64 * GP_WAVES) void graphs_prepare_kernel(eco_graph
   }
 }
 
+// Float-weighted sets (gs.edge_weights, EdgeType.RANDOM): float64 sums must not depend on arrival order, so no
+// atomics -- each row is summed by ONE lane in CSR order (lane t of the graph takes rows t, t + 64 WPG, ...), the
+// lane partials are combined by the fixed xor butterfly and the graph's waves in wave order: bitwise reproducible
+// run to run.  meta as score_solver.py:353-375: {max over nonzero row sums, max(1, sum_{w>0} w / 2),
+// min(0, sum_{w<0} w / 2), sum w}.
+template <int WPG>
+__global__ __launch_bounds__(64 * GP_WAVES) void graphs_prepare_weighted_kernel(eco_graph_set gs, int first,
+                                                                                int count) {
+  constexpr int GPB = GP_WAVES / WPG;
+  constexpr int NTG = 64 * WPG;
+  const int lane = threadIdx.x & 63;
+  const int gl = (int)threadIdx.x / NTG;
+  const int tg = (int)threadIdx.x % NTG;
+  const int g = first + blockIdx.x * GPB + gl;
+  const bool live = g < first + count;
+  if (WPG == 1 && !live) return;
+  const int N = gs.n_spins;
+  double pos = 0.0, neg = 0.0, sum = 0.0, best = -INFINITY;
+  int mdeg = 1, has = 0;
+  if (live) {
+    const int32_t* rp = gs.row_ptr + (size_t)g * (N + 1);
+    const double* ew = gs.edge_weights + gs.edge_base[g];
+    for (int v = tg; v < N; v += NTG) {
+      double rs = 0.0;
+      int d = 0;
+      const int q1 = rp[v + 1];
+      for (int q = rp[v]; q < q1; ++q) {
+        const double w = ew[q];
+        rs += w;
+        if (w > 0.0) pos += w; else neg += w;
+        d += (w != 0.0);
+      }
+      sum += rs;
+      gs.deg[(size_t)g * N + v] = d;
+      mdeg = max(mdeg, max(d, 1));
+      if (rs != 0.0) { has = 1; best = fmax(best, rs); }  // mlr = max over NONZERO entries
+    }
+  }
+  pos = wave_sum_d(pos);
+  neg = wave_sum_d(neg);
+  sum = wave_sum_d(sum);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_xor(best, o, 64));
+  mdeg = wave_max_i(mdeg);
+  has = wave_max_i(has);
+  if (WPG > 1) {  // combine the graph's waves in wave order
+    __shared__ double rpos[GP_WAVES], rneg[GP_WAVES], rsm[GP_WAVES], rbest[GP_WAVES];
+    __shared__ int rmd[GP_WAVES], rhas[GP_WAVES];
+    const int wv = threadIdx.x >> 6;
+    if (lane == 0) { rpos[wv] = pos; rneg[wv] = neg; rsm[wv] = sum; rbest[wv] = best; rmd[wv] = mdeg; rhas[wv] = has; }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int k = 1; k < WPG; ++k) {
+      pos += rpos[k]; neg += rneg[k]; sum += rsm[k];
+      best = fmax(best, rbest[k]); mdeg = max(mdeg, rmd[k]); has = max(has, rhas[k]);
+    }
+    if (!live) return;
+  }
+  if (lane == 0) {
+    gs.max_deg[g] = mdeg;
+    gs.valid[g] = has;
+    double* m = gs.meta + (size_t)g * 4;
+    m[0] = has ? best : 1.0;
+    const double q = pos / 2.0;
+    m[1] = q > 1.0 ? q : 1.0;
+    const double lb = neg / 2.0;
+    m[2] = lb < 0.0 ? lb : 0.0;
+    m[3] = sum;
+  }
+}
+
 // ------------------------------------------------------------- env kernels ----
 // time table: tab[k] = running f64 sum of k additions of 1/T (spinsystem.py:493, :506)
 __global__ void build_time_table_kernel(uint8_t* state, size_t off_tab, int T) {
@@ -130,8 +201,8 @@ __global__ void build_time_table_kernel(uint8_t* state, size_t off_tab, int T) {
   *hdr = T;
 }
 
-template <int VPT>
-__device__ __forceinline__ void write_obs(const EnvArgs& a, int e, int lane, const int (&s)[VPT], const int (&h)[VPT],
+template <int VPT, class F>
+__device__ __forceinline__ void write_obs(const EnvArgs& a, int e, int lane, const int (&s)[VPT], const F (&h)[VPT],
                                           const int (&tsf)[VPT], const ObsCtx& c) {
   const int N = a.cfg.n_spins;
   const int nobs = a.cfg.n_obs;
@@ -162,16 +233,17 @@ __device__ __forceinline__ void write_obs(const EnvArgs& a, int e, int lane, con
 // never within 2^-53 of an f32 rounding midpoint without being one (its distance from any K / 2^j is at least
 // 2^-42 relative), so rounding through float64 cannot change the f32 result.  -0.0 is kept (the product is a
 // float product: s = -1, h = 0 gives -0.0, as the reference's float64 product does).  tests/test_env_gpu.py
-// checks these rows bitwise against the general path.
+// checks these rows bitwise against the general path.  None of that carries over to float weights (F = double):
+// there s * h / mlr is computed in float64, as the general path does, and rounded once to f32.
 __device__ __forceinline__ bool obs_default_layout(const eco_env_config& c) {
   return c.n_obs == 7 && c.obs_ids[0] == ECO_OBS_SPIN_STATE && c.obs_ids[1] == ECO_OBS_IMMEDIATE_QUALITY_CHANGE &&
          c.obs_ids[2] == ECO_OBS_TIME_SINCE_FLIP && c.obs_ids[3] == ECO_OBS_DISTANCE_FROM_BEST_SOLUTION &&
          c.obs_ids[4] == ECO_OBS_DISTANCE_FROM_BEST_STATE && c.obs_ids[5] == ECO_OBS_NUMBER_OF_QUALITY_IMPROVEMENTS &&
          c.obs_ids[6] == ECO_OBS_TERMINATION_IMMANENCY;
 }
-template <int VPT>
+template <int VPT, class F>
 __device__ __forceinline__ void write_obs_default(const EnvArgs& a, int e, int lane, const int (&s)[VPT],
-                                                  const int (&h)[VPT], const int (&tsf)[VPT], const ObsCtx& c) {
+                                                  const F (&h)[VPT], const int (&tsf)[VPT], const ObsCtx& c) {
   const int N = a.cfg.n_spins;
   const double* tab = tab_ptr(a);
   const float mlrf = (float)c.mlr;
@@ -183,7 +255,9 @@ __device__ __forceinline__ void write_obs_default(const EnvArgs& a, int e, int l
     if (v >= N) continue;
     const float sf = (float)s[k];
     const float x0 = binary ? (float)((1 - s[k]) / 2) : sf;  // (1 - s) / 2 is exact: 0 or 1
-    const float x1 = __fdiv_rn(sf * (float)h[k], mlrf);
+    float x1;
+    if constexpr (std::is_same_v<F, int>) x1 = __fdiv_rn(sf * (float)h[k], mlrf);
+    else x1 = (float)(((double)s[k] * h[k]) / c.mlr);
     const float x2 = (float)tab[tsf[k]];
     float4* dst = (float4*)(a.obs_x + ((size_t)e * N + v) * 8);
     dst[0] = make_float4(x0, x1, x2, u3);
@@ -192,8 +266,11 @@ __device__ __forceinline__ void write_obs_default(const EnvArgs& a, int e, int l
 }
 
 // SpinSystemBase.reset (spinsystem.py:183-259) + _reset_state (:283-330)
-template <int VPT>
+// F = int: integer weights (the packed byte); F = double: float-weighted sets (gs.edge_weights), every quantity the
+// reference computes in float64 computed in float64 here.
+template <int VPT, class F = int>
 __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
+  constexpr bool FW = std::is_same_v<F, double>;
   extern __shared__ int8_t s_lds[];  // [4 waves][N] spins staged for the J.s matvec
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -210,8 +287,9 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
   }
   const double* meta = a.gs.meta + (size_t)gid * 4;
   const double mlr = meta[0], qn = meta[1], lb = meta[2];
-  const long long sumJ = (long long)meta[3];
-  int s[VPT], h[VPT], g[VPT], tsf[VPT];
+  const std::conditional_t<FW, double, long long> sumJ = (std::conditional_t<FW, double, long long>)meta[3];
+  int s[VPT], tsf[VPT];
+  F h[VPT], g[VPT];
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
@@ -236,16 +314,21 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
-  long long sg = 0;
+  std::conditional_t<FW, double, long long> sg = 0;
   int cnt = 0;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    int hv = 0;
+    F hv = 0;
     if (v < N) {
-      for (int q = rp[v]; q < rp[v + 1]; ++q) {
-        const uint32_t x = ed[q];
-        hv += edge_w(x) * (int)my_s[edge_col(x)];
+      if constexpr (FW) {
+        const double* ew = a.gs.edge_weights + a.gs.edge_base[gid];
+        for (int q = rp[v]; q < rp[v + 1]; ++q) hv += ew[q] * (double)my_s[edge_col(ed[q])];  // CSR order
+      } else {
+        for (int q = rp[v]; q < rp[v + 1]; ++q) {
+          const uint32_t x = ed[q];
+          hv += edge_w(x) * (int)my_s[edge_col(x)];
+        }
       }
     }
     h[k] = hv;
@@ -253,15 +336,16 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
     sg += g[k];
     cnt += (g[k] > 0);
   }
-  sg = wave_sum_ll(sg);
+  if constexpr (FW) sg = wave_sum_d(sg); else sg = wave_sum_ll(sg);
   cnt = wave_sum_i(cnt);
   // calculate_cut = 1/4 sum J (1 - s s^T) = (sum J - s.Js)/4, exact integer for integer weights
-  const double cut = (double)((sumJ - sg) / 4);
+  double cut;
+  if constexpr (FW) cut = (sumJ - sg) / 4.0; else cut = (double)((sumJ - sg) / 4);
   const double lbabs = lb < 0.0 ? -lb : lb;
   const double score = cut + lbabs;        // MaximizationProblem.get_score (score_solver.py:182-188)
   const double nscore = score / qn;        // get_normalized_score (:190-194)
   int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gh = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
+  F* gh = (F*)(a.state + L.off_field) + (size_t)e * N;
   int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
   int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
 #pragma unroll
@@ -287,7 +371,7 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
   ObsCtx c;
   c.mlr = mlr; c.dist_best = 0.0; c.hamming = 0.0; c.nqi = (double)cnt / (double)N;
   c.term = 0.0; c.ep_time = 0.0; c.basis = a.cfg.spin_basis;
-  write_obs<VPT>(a, e, lane, s, h, tsf, c);
+  write_obs<VPT, F>(a, e, lane, s, h, tsf, c);
 }
 
 // Optional per-phase stamps of env_step_kernel (timing build only: make timing; tools/r04/env_timing.py):
@@ -307,9 +391,13 @@ __device__ unsigned long long eco_env_ts[ECO_ENV_TS_EPS * 8];
 
 // SpinSystemBase.step (spinsystem.py:355-559), ExtraAction.NONE, memory_length None.
 // FASTOBS: DEFAULT_OBSERVABLES, fp32 rows only (write_obs_default).
-template <int VPT, bool FASTOBS>
+// F = double (float-weighted sets): h is an f64 register array updated along the CSR row of the flip as
+// h_j -= 2 w_aj s_a, the LDS row-delta slice is f64 (8 N bytes per wave), and score / nscore / best_* / rewards /
+// observation rows are the reference's float64 operations in its order (spinsystem.py:393-535).
+template <int VPT, bool FASTOBS, class F = int>
 __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
-  extern __shared__ int32_t d_lds[];  // [4 waves][N] row deltas
+  constexpr bool FW = std::is_same_v<F, double>;
+  extern __shared__ int32_t d_lds[];  // [4 waves][N] row deltas (int32, or f64 for F = double)
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
   const int e = uniform_i(blockIdx.x * 4 + wv);
@@ -330,21 +418,23 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
   }
   const int t = sc->t + 1;  // :362
   int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gh = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
+  F* gh = (F*)(a.state + L.off_field) + (size_t)e * N;
   int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
   int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
   const int gid = sc->graph;
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
   const int q0 = rp[act], q1 = rp[act + 1];
-  int s[VPT], h[VPT], tsf[VPT], bs[VPT], g[VPT];
+  int s[VPT], tsf[VPT], bs[VPT];
+  F h[VPT], g[VPT];
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
     if (v < N) { s[k] = gsp[v]; h[k] = gh[v]; tsf[k] = gt[v]; bs[k] = gb[v]; }
     else { s[k] = 0; h[k] = 0; tsf[k] = 0; bs[k] = 0; }
   }
-  int sa_old, ha;
+  int sa_old;
+  F ha;
   read_vertex<VPT>(s, h, act, sa_old, ha);
   ECO_ENV_TS(1);
   const double qn = sc->qn, mlr = sc->mlr;
@@ -355,8 +445,18 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
   // incremental local field: h_j -= 2 w_aj s_a(old) over the CSR row of `act`
   const bool track = a.cfg.has_basin_reward || a.cfg.has_stag_punishment;
   HistProbe hp;
-  row_update<VPT>(d_lds + wv * N, ed, q0, q1, N, lane, h, [&](int w) { return -2 * w * sa_old; },
-                  [&] { if (track) history_probe(a, e, sc->hash, act, hp); });
+  if constexpr (FW) {
+    const double* ew = a.gs.edge_weights + a.gs.edge_base[gid];
+    const double m2s = -2.0 * (double)sa_old;
+    // the same dynamic LDS seen as f64 [4 waves][N]: its own declaration carries the alignment of the 8-byte
+    // accesses, whatever static LDS a later change may put in front of it
+    extern __shared__ __attribute__((aligned(16))) double dd_lds[];
+    row_update<VPT>(dd_lds + wv * N, ed, q0, q1, N, lane, h,
+                    [&](int, int q) { return m2s * ew[q]; });
+  } else {
+    row_update<VPT>(d_lds + wv * N, ed, q0, q1, N, lane, h, [&](int w) { return -2 * w * sa_old; },
+                    [&] { if (track) history_probe(a, e, sc->hash, act, hp); });
+  }
   ECO_ENV_TS(2);
   // flip + time-since-flip counters (:397, :492-497)
   int cnt = 0;
@@ -374,7 +474,11 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
 #pragma unroll
     for (int k = 0; k < VPT; ++k) c += __popcll(__ballot(s[k] < 0)); return c; }();
   // HistoryBuffer.update (utils.py:444-464): is the flipped set (== spin configuration) new?
-  const bool isnew = track ? history_update_from<VPT>(a, e, lane, sc, hp, words) : true;
+  // (the f64 step probes the visited set here, without the early first-slot load: the probe record that
+  // history_update_from carries across the field update is the integer kernels' one stack object)
+  bool isnew = true;
+  if constexpr (FW) { if (track) isnew = history_update<VPT>(a, e, lane, sc, act, words); }
+  else isnew = track ? history_update_from<VPT>(a, e, lane, sc, hp, words) : true;
   ECO_ENV_TS(3);
   // reward (:418-457)
   double best_score = sc->best_score, best_nscore = sc->best_nscore;
@@ -435,13 +539,13 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
   c.term = x > 0.0 ? x : 0.0;                                         // :509-511
   c.ep_time = tab_ptr(a)[t];                                          // :506
   c.basis = a.cfg.spin_basis;
-  if (FASTOBS) write_obs_default<VPT>(a, e, lane, s, h, tsf, c);
-  else write_obs<VPT>(a, e, lane, s, h, tsf, c);
+  if (FASTOBS) write_obs_default<VPT, F>(a, e, lane, s, h, tsf, c);
+  else write_obs<VPT, F>(a, e, lane, s, h, tsf, c);
   ECO_ENV_TS(5);
 }
-template <int VPT, bool FASTOBS>
+template <int VPT, bool FASTOBS, class F = int>
 __global__ __launch_bounds__(256) void env_step_kernel(EnvArgs a) {
-  env_step_body<VPT, FASTOBS>(a);
+  env_step_body<VPT, FASTOBS, F>(a);
 }
 // The training / bench configuration up to N = 256 at 8 waves per SIMD (<= 64 VGPRs, no spills): all 8192
 // ER-200 episodes of a step are resident at once (one wave each) instead of 6144 plus a second round of 2048
@@ -455,7 +559,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 // cut change g = s * (J s) (first index on ties); an episode whose best change is negative is
 // finished (the solver stops, :124-127) and is marked done so later steps leave it unchanged.
 // Irreversible envs consider only still-flippable vertices (s == -1, :117-121).
-template <int VPT>
+template <int VPT, class F = int>
 __global__ __launch_bounds__(256) void env_greedy_kernel(EnvArgs a, int32_t* actions) {
   const int lane = threadIdx.x & 63;
   const int e = uniform_i(blockIdx.x * 4 + (threadIdx.x >> 6));
@@ -467,22 +571,25 @@ __global__ __launch_bounds__(256) void env_greedy_kernel(EnvArgs a, int32_t* act
     return;
   }
   const int8_t* gsp = (const int8_t*)(a.state + a.L.off_spins) + (size_t)e * N;
-  const int32_t* gh = (const int32_t*)(a.state + a.L.off_field) + (size_t)e * N;
-  int best = INT_MIN, bi = 0x7fffffff;
+  const F* gh = (const F*)(a.state + a.L.off_field) + (size_t)e * N;
+  F best;
+  if constexpr (std::is_same_v<F, double>) best = -INFINITY; else best = INT_MIN;
+  int bi = 0x7fffffff;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
     if (v < N) {
       const int s = gsp[v];
       if (a.cfg.reversible_spins || s < 0) {
-        const int g = s * gh[v];
+        const F g = s * gh[v];
         if (g > best || (g == best && v < bi)) { best = g; bi = v; }
       }
     }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    const int ob = __shfl_xor(best, o, 64), oi = __shfl_xor(bi, o, 64);
+    const F ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
   if (lane == 0) {
@@ -540,6 +647,10 @@ static int validate_cfg(const eco_env_config* c) {
   if (c->spin_basis != ECO_BASIS_SIGNED && c->spin_basis != ECO_BASIS_BINARY)
     return fail(ECO_ERR_BASIS, "Unrecognised SpinBasis");
   if (c->horizon_length < 1) return fail(ECO_ERR_ARG, "horizon_length must be >= 1");
+  if (c->float_weights != 0 && c->float_weights != 1) return fail(ECO_ERR_ARG, "float_weights must be 0 or 1");
+  if (c->float_weights && t != ECO_TARGET_CUT)
+    return fail(ECO_ERR_ARG, "float edge weights run OptimisationTarget.CUT only (the generic-scorer kernels are "
+                             "integer)");
   return ECO_OK;
 }
 
@@ -548,6 +659,17 @@ static int validate_gs(const eco_graph_set* gs, int N) {
     return fail(ECO_ERR_ARG, "incomplete graph set");
   if (gs->n_spins != N) return fail(ECO_ERR_ARG, "graph set n_spins does not match the env");
   if (gs->n_graphs < 1) return fail(ECO_ERR_ARG, "empty graph set");
+  if (gs->edge_weights && gs->unit_weights)
+    return fail(ECO_ERR_ARG, "graph set has float edge_weights and unit_weights set");
+  return ECO_OK;
+}
+
+// the env's field type must match the graph set's weight kind
+static int check_weight_kind(const eco_env_config* c, const eco_graph_set* gs) {
+  if ((c->float_weights != 0) != (gs->edge_weights != nullptr))
+    return fail(ECO_ERR_ARG, c->float_weights ? "env configured with float_weights but the graph set has no edge_weights"
+                                              : "float-weighted graph set needs an env configured with float_weights "
+                                                "(OptimisationTarget.CUT only)");
   return ECO_OK;
 }
 
@@ -589,6 +711,14 @@ int eco::graphs_prepare_range(eco_graph_set* gs, int first, int count, hipStream
     return fail(ECO_ERR_ARG, "incomplete graph set");
   if (gs->n_graphs < 1 || gs->n_spins < 1) return fail(ECO_ERR_ARG, "empty graph set");
   if (first < 0 || count < 1 || first + count > gs->n_graphs) return fail(ECO_ERR_ARG, "graph range out of set");
+  if (gs->edge_weights) {
+    if (gs->unit_weights) return fail(ECO_ERR_ARG, "graph set has float edge_weights and unit_weights set");
+    if (gs->n_spins <= 512)
+      graphs_prepare_weighted_kernel<1><<<(count + GP_WAVES - 1) / GP_WAVES, 64 * GP_WAVES, 0, st>>>(*gs, first, count);
+    else
+      graphs_prepare_weighted_kernel<GP_WAVES><<<count, 64 * GP_WAVES, 0, st>>>(*gs, first, count);
+    return check_launch("graphs_prepare");
+  }
   if (gs->n_spins <= 512) {
     const size_t lds = (size_t)GP_WAVES * (3 * gs->n_spins + 1) * sizeof(int);
     (void)hipFuncSetAttribute((const void*)graphs_prepare_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -625,7 +755,7 @@ extern "C" size_t eco_graphs_adjbits_bytes(int32_t n_spins, int32_t n_graphs) {
 
 extern "C" size_t eco_env_state_bytes(const eco_env_config* cfg, int32_t batch) {
   if (validate_cfg(cfg) != ECO_OK || batch < 1) return 0;
-  return env_layout(cfg->n_spins, cfg->max_steps, batch).total;
+  return env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights).total;
 }
 
 static int make_args(EnvArgs& a, const eco_env_config* cfg, const eco_graph_set* gs, void* state, int32_t batch) {
@@ -637,7 +767,7 @@ static int make_args(EnvArgs& a, const eco_env_config* cfg, const eco_graph_set*
   a = EnvArgs{};
   a.cfg = *cfg;
   if (gs) a.gs = *gs;
-  a.L = env_layout(cfg->n_spins, cfg->max_steps, batch);
+  a.L = env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights);
   a.state = (uint8_t*)state;
   a.B = batch;
   a.err = err_word();
@@ -653,6 +783,8 @@ extern "C" int eco_env_reset(const eco_env_config* cfg, const eco_graph_set* gs,
   if (rc) return rc;
   if (!gs) return fail(ECO_ERR_ARG, "null graph set");
   if (!graph_ids) return fail(ECO_ERR_ARG, "null graph_ids");
+  rc = check_weight_kind(cfg, gs);
+  if (rc) return rc;
   a.graph_ids = graph_ids; a.spins_in = spins; a.mask = reset_mask; a.seed = seed;
   a.obs_x = obs_x; a.obs_f64 = obs_f64;
   hipStream_t st = (hipStream_t)stream;
@@ -660,7 +792,8 @@ extern "C" int eco_env_reset(const eco_env_config* cfg, const eco_graph_set* gs,
   const int blocks = (batch + 3) / 4;
   const size_t lds = (size_t)4 * cfg->n_spins;
   if (generic_target(cfg)) return env_reset_problem_launch(a, blocks, lds, st);
-  ECO_DISPATCH_VPT(cfg->n_spins, (env_reset_kernel<V><<<blocks, 256, lds, st>>>(a)));
+  if (cfg->float_weights) ECO_DISPATCH_VPT(cfg->n_spins, (env_reset_kernel<V, double><<<blocks, 256, lds, st>>>(a)));
+  else ECO_DISPATCH_VPT(cfg->n_spins, (env_reset_kernel<V><<<blocks, 256, lds, st>>>(a)));
   return check_launch("env_reset");
 }
 
@@ -694,6 +827,8 @@ extern "C" int eco_env_step(const eco_env_config* cfg, const eco_graph_set* gs, 
   if (rc) return rc;
   if (!gs) return fail(ECO_ERR_ARG, "null graph set");
   if (!actions || !rewards || !dones) return fail(ECO_ERR_ARG, "null actions/rewards/dones");
+  rc = check_weight_kind(cfg, gs);
+  if (rc) return rc;
   a.actions = actions; a.rewards = rewards; a.dones = dones; a.obs_x = obs_x; a.obs_f64 = obs_f64;
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (batch + 3) / 4;
@@ -705,6 +840,12 @@ extern "C" int eco_env_step(const eco_env_config* cfg, const eco_graph_set* gs, 
                     cfg->obs_ids[4] == ECO_OBS_DISTANCE_FROM_BEST_STATE &&
                     cfg->obs_ids[5] == ECO_OBS_NUMBER_OF_QUALITY_IMPROVEMENTS &&
                     cfg->obs_ids[6] == ECO_OBS_TERMINATION_IMMANENCY;
+  if (cfg->float_weights) {  // f64 field and row deltas: [4 waves][N] f64 of LDS (64 KB at N = 2048)
+    const size_t ldsw = (size_t)32 * cfg->n_spins;  // <= 64 KB: within the default dynamic LDS limit
+    if (fast) ECO_DISPATCH_VPT(cfg->n_spins, (env_step_kernel<V, true, double><<<blocks, 256, ldsw, st>>>(a)));
+    else ECO_DISPATCH_VPT(cfg->n_spins, (env_step_kernel<V, false, double><<<blocks, 256, ldsw, st>>>(a)));
+    return check_launch("env_step");
+  }
   const size_t lds = (size_t)16 * cfg->n_spins;
   if (fast && cfg->n_spins <= 64) env_step_fast_kernel<1><<<blocks, 256, lds, st>>>(a);
   else if (fast && cfg->n_spins <= 128) env_step_fast_kernel<2><<<blocks, 256, lds, st>>>(a);
@@ -720,12 +861,16 @@ extern "C" int eco_env_greedy_actions(const eco_env_config* cfg, const eco_graph
   int rc = make_args(a, cfg, gs, state, batch);
   if (rc) return rc;
   if (!actions) return fail(ECO_ERR_ARG, "null actions");
+  if (gs && (rc = check_weight_kind(cfg, gs))) return rc;
   if (cfg->optimisation_target == ECO_TARGET_MIN_DOM_SET && !gs)
     return fail(ECO_ERR_ARG, "MIN_DOM_SET greedy actions need the graph set");
   const int blocks = (batch + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
   if (generic_target(cfg)) return env_greedy_problem_launch(a, actions, blocks, (size_t)4 * cfg->n_spins, st);
-  ECO_DISPATCH_VPT(cfg->n_spins, (env_greedy_kernel<V><<<blocks, 256, 0, st>>>(a, actions)));
+  if (cfg->float_weights)
+    ECO_DISPATCH_VPT(cfg->n_spins, (env_greedy_kernel<V, double><<<blocks, 256, 0, st>>>(a, actions)));
+  else
+    ECO_DISPATCH_VPT(cfg->n_spins, (env_greedy_kernel<V><<<blocks, 256, 0, st>>>(a, actions)));
   return check_launch("env_greedy");
 }
 

@@ -2,6 +2,7 @@
 // generic-scorer kernels (eco_env_problems.hip).
 #pragma once
 #include "eco_common.h"
+#include <type_traits>
 
 namespace eco {
 
@@ -46,7 +47,9 @@ struct ObsCtx {
 };
 // g is passed as the field h; the reference's g = s * (J@s) is a float64 product, so
 // s = -1 with h = +0.0 gives -0.0 (kept: observations are compared bitwise).
-__device__ __forceinline__ double obs_value(int id, const ObsCtx& c, int s, int h, int tsfk, const double* tab) {
+// F: the field type, int (integer weights) or double (float-weighted sets: the same f64 operations).
+template <class F>
+__device__ __forceinline__ double obs_value(int id, const ObsCtx& c, int s, F h, int tsfk, const double* tab) {
   switch (id) {
     case ECO_OBS_SPIN_STATE: return c.basis == ECO_BASIS_BINARY ? (double)(1 - s) / 2.0 : (double)s;
     case ECO_OBS_IMMEDIATE_QUALITY_CHANGE: return ((double)s * (double)h) / c.mlr;
@@ -68,15 +71,23 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+__device__ __forceinline__ int readlane_t(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ double readlane_t(double v, int lane) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)(b & 0xFFFFFFFFll), lane);
+  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+  return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
 // Pre-flip spin and field of vertex `act` (lane act & 63, slot act >> 6) from the wave's registers.
-template <int VPT>
-__device__ __forceinline__ void read_vertex(const int (&s)[VPT], const int (&f)[VPT], int act, int& sa, int& fa) {
+template <int VPT, class F>
+__device__ __forceinline__ void read_vertex(const int (&s)[VPT], const F (&f)[VPT], int act, int& sa, F& fa) {
   const int kk = act >> 6, la = act & 63;
   sa = 0;
   fa = 0;
 #pragma unroll
   for (int k = 0; k < VPT; ++k)
-    if (k == kk) { sa = __builtin_amdgcn_readlane(s[k], la); fa = __builtin_amdgcn_readlane(f[k], la); }
+    if (k == kk) { sa = __builtin_amdgcn_readlane(s[k], la); fa = readlane_t(f[k], la); }
 }
 
 // f_j += coef(J_ja) for every neighbour j of `act`: the lanes load the CSR row in parallel and scatter the
@@ -85,10 +96,16 @@ __device__ __forceinline__ void read_vertex(const int (&s)[VPT], const int (&f)[
 struct NoIssue {
   __device__ void operator()() const {}
 };
+// coef takes the packed word's integer weight, or (float-weighted sets) the edge index q whose f64 weight it loads
+template <class Coef>
+__device__ __forceinline__ auto row_coef(Coef& coef, uint32_t x, int q) {
+  if constexpr (std::is_invocable_v<Coef&, int, int>) return coef(edge_w(x), q);
+  else return coef(edge_w(x));
+}
 // after_loads: issued right after the row's edge loads (the step's next loads, e.g. the visited-set probe)
-template <int VPT, class Coef, class After = NoIssue>
-__device__ __forceinline__ void row_update(int32_t* dl, const uint32_t* ed, int q0, int q1, int N, int lane,
-                                           int (&f)[VPT], Coef coef, After after_loads = After()) {
+template <int VPT, class F, class Coef, class After = NoIssue>
+__device__ __forceinline__ void row_update(F* dl, const uint32_t* ed, int q0, int q1, int N, int lane,
+                                           F (&f)[VPT], Coef coef, After after_loads = After()) {
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
@@ -98,12 +115,12 @@ __device__ __forceinline__ void row_update(int32_t* dl, const uint32_t* ed, int 
   if (q1 - q0 <= 64) {  // one load per lane (every ER-200 / BA-500 row): the caller's next loads go out behind it
     const uint32_t x = q0 + lane < q1 ? ed[q0 + lane] : 0u;
     after_loads();
-    if (q0 + lane < q1) dl[edge_col(x)] = coef(edge_w(x));
+    if (q0 + lane < q1) dl[edge_col(x)] = row_coef(coef, x, q0 + lane);
   } else {
     after_loads();
     for (int q = q0 + lane; q < q1; q += 64) {
       const uint32_t x = ed[q];
-      dl[edge_col(x)] = coef(edge_w(x));
+      dl[edge_col(x)] = row_coef(coef, x, q);
     }
   }
   wave_lds_sync();
@@ -218,6 +235,7 @@ __device__ __forceinline__ bool history_update_from(const EnvArgs& a, int e, int
 
 // vertices per lane for N spins (one 64-lane wave per episode)
 // dynamic LDS of the step kernels: int32 row deltas [4 waves][N], then MinDomSet codes [4][N]
+// (the float-weighted CUT step: f64 row deltas [4 waves][N], 64 KB at N = 2048)
 inline size_t env_step_lds(int N) { return (size_t)4 * N * 4 + (size_t)4 * N; }
 
 #define ECO_DISPATCH_VPT(N, CALL)                                   \

@@ -10,7 +10,9 @@
 // BA: preferential attachment exactly as networkx.barabasi_albert_graph (initial star of m
 //     targets, repeated-nodes list, m distinct draws per new vertex); the process is
 //     sequential per graph, so one wave owns one graph with its lists in LDS.
-// Weights: +-1 fair per edge (EdgeType.DISCRETE, symmetric hash) or 1 (UNIFORM).
+// Weights: +-1 fair per edge (EdgeType.DISCRETE, symmetric hash), 1 (UNIFORM), or float64 uniform in (-1, 1)
+// (EdgeType.RANDOM): w = 2u - 1, u the top 53 bits of the same symmetric hash, written to gs.edge_weights with
+// sign(w) in the packed word.
 // Parity is distributional only (different RNG streams from numpy/networkx).
 #include "eco_common.h"
 
@@ -26,6 +28,26 @@ __device__ __forceinline__ bool er_edge(uint64_t seed, int g, int i, int j, int 
 __device__ __forceinline__ int edge_sign(uint64_t seed, int g, int i, int j, int N, int discrete) {
   if (!discrete) return 1;
   return (rng3(seed ^ 0x5157A3C1ull, (uint64_t)g, pair_key(i, j, N)) >> 63) ? 1 : -1;
+}
+// ECO_WEIGHTS_RANDOM: 2u - 1 with u a 53-bit draw keyed by (seed, graph, unordered pair); exact in float64.  A draw of
+// exactly 0 (probability 2^-53) becomes 2^-53: stored weights are nonzero.
+__device__ __forceinline__ double edge_weight_random(uint64_t seed, int g, int i, int j, int N) {
+  const uint64_t r = rng3(seed ^ 0x5157A3C1ull, (uint64_t)g, pair_key(i, j, N));
+  const double w = 2.0 * ((double)(r >> 11) * 0x1p-53) - 1.0;
+  return w == 0.0 ? 0x1p-53 : w;
+}
+// packed word and (kind RANDOM) float64 weight of edge {i, j} stored at slot q of the graph's row data
+__device__ __forceinline__ void store_edge(uint32_t* ed, double* ew, long long q, int col, uint64_t seed, int g, int i,
+                                           int j, int N, int kind) {
+  int w;
+  if (kind == ECO_WEIGHTS_RANDOM) {
+    const double wd = edge_weight_random(seed, g, i, j, N);
+    ew[q] = wd;
+    w = wd > 0.0 ? 1 : -1;
+  } else {
+    w = edge_sign(seed, g, i, j, N, kind);
+  }
+  ed[q] = (uint32_t)col | ((uint32_t)(uint8_t)(int8_t)w << 24);
 }
 
 // pass 1: per-row degree (wave per row)
@@ -78,8 +100,9 @@ __global__ void er_scan_kernel(int first, int count, int N, const int32_t* row_c
 }
 
 // pass 3: fill sorted columns (wave per row)
-__global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t seed, int discrete,
-                               const int32_t* row_ptr, const int64_t* edge_base, uint32_t* edges, long long cap) {
+__global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t seed, int kind,
+                               const int32_t* row_ptr, const int64_t* edge_base, uint32_t* edges, double* weights,
+                               long long cap) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long long)count * N) return;
@@ -88,6 +111,7 @@ __global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t se
   const int32_t* rp = row_ptr + (size_t)g * (N + 1);
   if (rp[N] > cap) return;
   uint32_t* ed = edges + edge_base[g];
+  double* ew = weights ? weights + edge_base[g] : nullptr;
   int pos = rp[i];
   for (int j0 = 0; j0 < N; j0 += 64) {
     const int j = j0 + lane;
@@ -95,8 +119,7 @@ __global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t se
     const uint64_t bal = __ballot(on);
     if (on) {
       const int k = __popcll(bal & ((1ull << lane) - 1ull));
-      const int w = edge_sign(seed, g, i, j, N, discrete);
-      ed[pos + k] = (uint32_t)j | ((uint32_t)(uint8_t)(int8_t)w << 24);
+      store_edge(ed, ew, pos + k, j, seed, g, i, j, N, kind);
     }
     pos += __popcll(bal);
   }
@@ -104,8 +127,8 @@ __global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t se
 
 // Barabasi-Albert (networkx.barabasi_albert_graph semantics), one wave per graph.
 // LDS per wave: repeated list [2 m (N - m)] int32, edge list [(N - m) m] x2 int16, degree [N], fill cursor [N]
-__global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int discrete, int32_t* row_ptr,
-                          const int64_t* edge_base, uint32_t* edges, long long cap, int32_t* err) {
+__global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int kind, int32_t* row_ptr,
+                          const int64_t* edge_base, uint32_t* edges, double* weights, long long cap, int32_t* err) {
   extern __shared__ int32_t sm[];
   const int lane = threadIdx.x;
   const int gi = blockIdx.x;
@@ -164,12 +187,12 @@ __global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int
   if (overflow) return;
   __syncthreads();
   uint32_t* ed = edges + edge_base[g];
+  double* ew = weights ? weights + edge_base[g] : nullptr;
   if (lane == 0) {  // deterministic fill order
     for (int e = 0; e < E; ++e) {
       const int a = es[e], b = et[e];
-      const int w = edge_sign(seed, g, a, b, N, discrete);
-      ed[cur[a]++] = (uint32_t)b | ((uint32_t)(uint8_t)(int8_t)w << 24);
-      ed[cur[b]++] = (uint32_t)a | ((uint32_t)(uint8_t)(int8_t)w << 24);
+      store_edge(ed, ew, cur[a]++, b, seed, g, a, b, N, kind);
+      store_edge(ed, ew, cur[b]++, a, seed, g, a, b, N, kind);
     }
   }
   __syncthreads();
@@ -177,12 +200,15 @@ __global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int
   for (int i = lane; i < N; i += 64) {
     for (int q = rp[i] + 1; q < rp[i + 1]; ++q) {
       const uint32_t x = ed[q];
+      const double xw = ew ? ew[q] : 0.0;
       int r = q - 1;
       while (r >= rp[i] && (ed[r] & 0xFFFFFFu) > (x & 0xFFFFFFu)) {
         ed[r + 1] = ed[r];
+        if (ew) ew[r + 1] = ew[r];
         --r;
       }
       ed[r + 1] = x;
+      if (ew) ew[r + 1] = xw;
     }
   }
 }
@@ -192,9 +218,18 @@ __global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int
 using namespace eco;
 
 extern "C" int eco_graphs_generate(eco_graph_set* gs, int32_t first, int32_t count, int32_t kind, double param,
-                                   int32_t discrete_weights, uint64_t seed, int64_t edge_cap, void* workspace,
+                                   int32_t weight_kind, uint64_t seed, int64_t edge_cap, void* workspace,
                                    eco_stream_t stream) {
   if (!gs || !gs->row_ptr || !gs->edges || !gs->edge_base) return fail(ECO_ERR_ARG, "incomplete graph set");
+  if (weight_kind < ECO_WEIGHTS_UNIFORM || weight_kind > ECO_WEIGHTS_RANDOM)
+    return fail(ECO_ERR_ARG, "unknown weight kind (0 = all 1, 1 = +-1, 2 = uniform in (-1, 1))");
+  if ((weight_kind == ECO_WEIGHTS_RANDOM) != (gs->edge_weights != nullptr))
+    return fail(ECO_ERR_ARG, weight_kind == ECO_WEIGHTS_RANDOM
+                                 ? "weight kind 2 (uniform in (-1, 1)) needs a graph set with edge_weights"
+                                 : "integer weight kinds cannot be generated into a float-weighted graph set");
+  if (gs->edge_weights && gs->unit_weights)
+    return fail(ECO_ERR_ARG, "graph set has float edge_weights and unit_weights set");
+  double* ewt = const_cast<double*>(gs->edge_weights);
   if (first < 0 || count < 1 || first + count > gs->n_graphs) return fail(ECO_ERR_ARG, "graph range out of set");
   const int N = gs->n_spins;
   hipStream_t st = (hipStream_t)stream;
@@ -210,8 +245,8 @@ extern "C" int eco_graphs_generate(eco_graph_set* gs, int32_t first, int32_t cou
     const int rblocks = (int)((rows + 3) / 4);
     er_count_kernel<<<rblocks, 256, 0, st>>>(first, count, N, (float)param, seed, cnt);
     er_scan_kernel<<<(count + 3) / 4, 256, 0, st>>>(first, count, N, cnt, rp, edge_cap, err);
-    er_fill_kernel<<<rblocks, 256, 0, st>>>(first, count, N, (float)param, seed, discrete_weights, rp, gs->edge_base,
-                                            ed, edge_cap);
+    er_fill_kernel<<<rblocks, 256, 0, st>>>(first, count, N, (float)param, seed, weight_kind, rp, gs->edge_base,
+                                            ed, ewt, edge_cap);
   } else if (kind == ECO_GRAPH_BA) {
     const int m = (int)param;
     if (m < 1 || m >= N || m > 64) return fail(ECO_ERR_ARG, "BA m must be in [1, min(N-1, 64)]");
@@ -219,7 +254,7 @@ extern "C" int eco_graphs_generate(eco_graph_set* gs, int32_t first, int32_t cou
     const size_t lds = (4 * E + 2 * (size_t)N) * sizeof(int32_t);
     if (lds > 160 * 1024) return fail(ECO_ERR_ARG, "BA graph too large for one workgroup's LDS");
     (void)hipFuncSetAttribute((const void*)ba_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    ba_kernel<<<count, 64, lds, st>>>(first, count, N, m, seed, discrete_weights, rp, gs->edge_base, ed, edge_cap,
+    ba_kernel<<<count, 64, lds, st>>>(first, count, N, m, seed, weight_kind, rp, gs->edge_base, ed, ewt, edge_cap,
                                       err);
   } else {
     return fail(ECO_ERR_ARG, "unknown graph kind");

@@ -207,7 +207,8 @@ __global__ void pack_kernel(const float* __restrict__ f, int nobs, float* __rest
 // streaming them from L2 in every wave.
 // LDS: Hs [rows_pad][LDH] | Wl [2][64][LDW] (WLDS) | Xs [rows_pad][8] (WLDS) or readout scratch |
 //      RI [rows_pad] int2 | GB [gpb] i64 | MD [gpb]
-template <int MAXT, bool SAVE, int NW, bool WLDS>
+// FW: float-weighted graph set (gs.edge_weights): every gather reads (float)edge_weights[q] instead of the packed byte
+template <int MAXT, bool SAVE, int NW, bool WLDS, bool FW = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forward_kernel(MpnnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   ECO_TS(0);
@@ -236,6 +237,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forwa
   const int s4 = lane >> 4;
   const int c16 = lane & 15;
   const uint32_t* __restrict__ edges = a.gs.edges;
+  const double* __restrict__ ewts = a.gs.edge_weights;  // FW only
 
   // ---- staging: x rows (WLDS, 8-float rows), row info, Wf ----
   const bool xwide = a.xw == 16;  // features 8..15 (read from global memory, never staged)
@@ -310,8 +312,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forwa
       float4 acc[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[c] = zero4();
-      for_edges(edges + (valid ? GB[r / N] : 0), ri.e0, ri.e1, [&](uint32_t ex) {
-        const float wv = (float)edge_w(ex);
+      const size_t gb = valid ? GB[r / N] : 0;
+      for_edges(edges + gb, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+        const float wv = edge_wf<FW>(ex, ewts + gb, q);
         const float* zr = Hs + (rbase + edge_col(ex)) * LDH + 4 * s4;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -401,8 +404,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forwa
         float4 agg[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) agg[c] = zero4();
-        const uint32_t* eg = edges + (valid ? GB[r / N] : 0);
-        if (!mfma_first) gather_ri(ri, eg, Hs, (r / N) * N, s4, agg);
+        const size_t gb = valid ? GB[r / N] : 0;
+        const uint32_t* eg = edges + gb;
+        if (!mfma_first) gather_ri<FW>(ri, eg, Hs, (r / N) * N, s4, agg, ewts + gb);
         // gather-independent half: d = Wm[:, 64:] . e ; hn = Wu[:, :64] . h
         f32x4 d[4];
         float4 hcur[4];
@@ -420,7 +424,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forwa
           mm_bf3_lean(hn[ti], hcur, BFL + 2 * BF_HALF, lane);
         }
         if (layer == 0 && ti == 0) ECO_TS(11);
-        if (mfma_first) gather_ri(ri, eg, Hs, (r / N) * N, s4, agg);
+        if (mfma_first) gather_ri<FW>(ri, eg, Hs, (r / N) * N, s4, agg, ewts + gb);
         if (layer == 0 && ti == 0) ECO_TS(12);
         // aggregation (A . h) / norm (mpnn.py:118), already in operand layout
         const float nf = (float)ri.norm;
@@ -500,7 +504,7 @@ __device__ __forceinline__ void bf3_t2(f32x4 (&d8)[8], const float4 (&x)[4], con
 // per-graph / per-block partials; eco_train.hip reduces dW = sum_nodes dY^T X.
 // LDS: G [rows_pad][LDH] (dq rows at the start) | Wl [2][128][LDH] (WLDS: Wu^T, Wm^T) | Xs [rows_pad][8] (WLDS) |
 //      RI [rows_pad] int2 | GB [gpb] i64 | DMEAN [gpb][64] | RED [(gpb < NW ? gpb : 1)][NW][64]
-template <int MAXT, int NW, bool WLDS>
+template <int MAXT, int NW, bool WLDS, bool FW = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backward_kernel(MpnnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   ECO_TS(16);
@@ -707,7 +711,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
         float4 acc[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[c] = valid ? f4(GR(GR_DH) + (R0 + r) * 64 + 16 * c + 4 * s4) : zero4();
-        gather_ri(ri, edges + (valid ? GB[r / N] : 0), G, (r / N) * N, s4, acc);
+        const size_t gb = valid ? GB[r / N] : 0;
+        gather_ri<FW>(ri, edges + gb, G, (r / N) * N, s4, acc, a.gs.edge_weights + gb);
 #pragma unroll
         for (int c = 0; c < 4; ++c) dh[ti][c] = acc[c];
       }
@@ -812,8 +817,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
 #pragma unroll
         for (int i = 0; i < 16; ++i) dz[i] = 0.f;
         const int rbase = (r / N) * N;
-        for_edges(edges + (valid ? GB[r / N] : 0), ri.e0, ri.e1, [&](uint32_t ex) {
-          const float wv = (float)edge_w(ex);
+        const size_t gb = valid ? GB[r / N] : 0;
+        for_edges(edges + gb, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+          const float wv = edge_wf<FW>(ex, a.gs.edge_weights + gb, q);
           const float* gi = G + (rbase + edge_col(ex)) * LDH + 4 * s4;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -871,7 +877,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
 // exact-f32 MFMA tiles as the LDS kernels with both layer weights staged in LDS (8 waves: the gathers
 // and the 8-chunk Linears need more than the 128 VGPRs of a 16-wave workgroup).
 // LDS: Wl [2][64][LDW] | readout scratch
-template <int NW>
+template <int NW, bool FW = false>
 __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs a, float* hbuf) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   ws_invalidate_key(a.call_maxdeg);  // hbuf overwrites the cached shared-graph tables
@@ -895,6 +901,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
   const int c16 = lane & 15;
   const int gid = a.gids[e];
   const uint32_t* __restrict__ eg = a.gs.edges + a.gs.edge_base[gid];
+  const double* __restrict__ ewg = a.gs.edge_weights + a.gs.edge_base[gid];  // FW only
   const float* x = a.x + R0 * 8;
   auto rinfo = [&](int r) { return row_info_packed(pack_row_info(a, e, r, N)); };
 
@@ -930,8 +937,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
       float4 acc[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[c] = zero4();
-      for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex) {
-        const float wv = (float)edge_w(ex);
+      for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+        const float wv = edge_wf<FW>(ex, ewg, q);
         const float* zr = HB + (size_t)edge_col(ex) * 64 + 4 * s4;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -986,8 +993,8 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
       float4 am[4], ev[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) am[c] = zero4();
-      for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex) {
-        const float wv = (float)edge_w(ex);
+      for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+        const float wv = edge_wf<FW>(ex, ewg, q);
         const float* hr = Hc + (size_t)edge_col(ex) * 64 + 4 * s4;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1059,6 +1066,10 @@ static int prepare(MpnnArgs& a, const float* packed, int32_t n_obs_in, const eco
   if (N < 1 || N > MPNN_MAX_SPINS_LARGE) return fail(ECO_ERR_ARG, "mpnn supports 1 <= N <= 2048");
   if (norm_scope != ECO_NORM_PER_GRAPH && norm_scope != ECO_NORM_PER_CALL)
     return fail(ECO_ERR_ARG, "bad norm_scope");
+  // a float-weighted set runs the CSR-gather kernels only: unit_weights == 0 keeps it off the dense, DL, shared-graph
+  // and fused-pair kernels (dense_eligible, dl_eligible and the shared-graph test all need unit_weights)
+  if (gs->edge_weights && gs->unit_weights)
+    return fail(ECO_ERR_ARG, "graph set has float edge_weights and unit_weights set");
   a = MpnnArgs{};
   a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = N; a.gpb = graphs_per_block(N, batch);
   a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
@@ -1256,6 +1267,12 @@ extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco
       return mpnn_forward_shared_launch(a, workspace, st);
     const int rows_pad = (N + 15) & ~15;
     const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
+    if (gs->edge_weights) {
+      (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      mpnn_forward_large_kernel<8, true><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256));
+      return check_launch("mpnn_forward_large");
+    }
     (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     mpnn_forward_large_kernel<8><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256));
@@ -1264,14 +1281,20 @@ extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco
   const int blocks = (batch + a.gpb - 1) / a.gpb;
   const KCfg k = pick_cfg(N, a.gpb, false);
   if (k.lds > LDS_MAX) return fail(ECO_ERR_ARG, "graph block exceeds the LDS budget");
-#define ECO_LAUNCH_FWD(MT, SV, NW, WL)                                                                          \
+  const bool fw = gs->edge_weights != nullptr;
+#define ECO_LAUNCH_FWD(MT, SV, NW, WL, FW)                                                                      \
   do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)mpnn_forward_kernel<MT, SV, NW, WL>,                                \
+    (void)hipFuncSetAttribute((const void*)mpnn_forward_kernel<MT, SV, NW, WL, FW>,                            \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);                        \
-    mpnn_forward_kernel<MT, SV, NW, WL><<<blocks, 64 * NW, k.lds, st>>>(a);                                   \
+    mpnn_forward_kernel<MT, SV, NW, WL, FW><<<blocks, 64 * NW, k.lds, st>>>(a);                               \
   } while (0)
-#define ECO_LAUNCH_FWD2(MT, NW, WL) \
-  do { if (saved) ECO_LAUNCH_FWD(MT, true, NW, WL); else ECO_LAUNCH_FWD(MT, false, NW, WL); } while (0)
+#define ECO_LAUNCH_FWD2(MT, NW, WL)                                     \
+  do {                                                                 \
+    if (fw && saved) ECO_LAUNCH_FWD(MT, true, NW, WL, true);           \
+    else if (fw) ECO_LAUNCH_FWD(MT, false, NW, WL, true);              \
+    else if (saved) ECO_LAUNCH_FWD(MT, true, NW, WL, false);           \
+    else ECO_LAUNCH_FWD(MT, false, NW, WL, false);                     \
+  } while (0)
   if (k.wlds && k.nw == 16 && k.maxt <= 1) ECO_LAUNCH_FWD2(1, 16, true);
   else if (k.wlds && k.nw == 8 && k.maxt <= 2) ECO_LAUNCH_FWD2(2, 8, true);
   else if (k.wlds && k.nw == 8) ECO_LAUNCH_FWD2(4, 8, true);
@@ -1314,12 +1337,15 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
   const int blocks = (batch + a.gpb - 1) / a.gpb;
   const KCfg k = pick_cfg(a.N, a.gpb, true);
   if (k.lds > LDS_MAX) return fail(ECO_ERR_ARG, "graph block exceeds the LDS budget");
-#define ECO_LAUNCH_BWD(MT, NW, WL)                                                                              \
+  const bool fw = gs->edge_weights != nullptr;
+#define ECO_LAUNCH_BWD1(MT, NW, WL, FW)                                                                         \
   do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)mpnn_backward_kernel<MT, NW, WL>,                                   \
+    (void)hipFuncSetAttribute((const void*)mpnn_backward_kernel<MT, NW, WL, FW>,                               \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);                        \
-    mpnn_backward_kernel<MT, NW, WL><<<blocks, 64 * NW, k.lds, st>>>(a);                                      \
+    mpnn_backward_kernel<MT, NW, WL, FW><<<blocks, 64 * NW, k.lds, st>>>(a);                                  \
   } while (0)
+#define ECO_LAUNCH_BWD(MT, NW, WL) \
+  do { if (fw) ECO_LAUNCH_BWD1(MT, NW, WL, true); else ECO_LAUNCH_BWD1(MT, NW, WL, false); } while (0)
   if (k.wlds && k.nw == 8 && k.maxt <= 2) ECO_LAUNCH_BWD(2, 8, true);
   else if (k.wlds && k.nw == 8) ECO_LAUNCH_BWD(4, 8, true);
   else if (k.wlds && k.maxt <= 4) ECO_LAUNCH_BWD(4, 4, true);
@@ -1328,6 +1354,7 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
   else if (k.maxt <= 8) ECO_LAUNCH_BWD(8, 4, false);
   else return fail(ECO_ERR_ARG, "graph block too large");
 #undef ECO_LAUNCH_BWD
+#undef ECO_LAUNCH_BWD1
   return check_launch("mpnn_backward");
 }
 

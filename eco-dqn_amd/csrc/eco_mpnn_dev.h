@@ -146,7 +146,8 @@ __device__ __forceinline__ void build_tile_schedule(int* SCH, const int2* RI, in
 }
 
 // Visit the packed edges [e0, e1): groups of 4 edge words, the next group's loads issued before
-// the current group is consumed (one exposed load latency per 4 edges instead of per edge).
+// the current group is consumed (one exposed load latency per 4 edges instead of per edge).  The body gets the edge
+// word and its index q relative to `edges` (the index of its float64 weight in a float-weighted set).
 template <typename F>
 __device__ __forceinline__ void for_edges(const uint32_t* __restrict__ edges, int e0, int e1, F&& f) {
   int q = e0;
@@ -162,21 +163,31 @@ __device__ __forceinline__ void for_edges(const uint32_t* __restrict__ edges, in
       for (int k = 0; k < 4; ++k) nxt[k] = edges[q + 4 + k];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) f(cur[k]);
+    for (int k = 0; k < 4; ++k) f(cur[k], q + k);
     q += 4;
     if (more) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
     }
   }
-  for (; q < e1; ++q) f(edges[q]);
+  for (; q < e1; ++q) f(edges[q], q);
+}
+
+// Edge weight inside the network, f32: the packed integer byte, or (FW: float-weighted set) the float64 weight
+// ew[q] rounded to f32 -- the reference feeds obs.float() (dqn.py:282, mpnn.py:50).
+template <bool FW>
+__device__ __forceinline__ float edge_wf(uint32_t ex, const double* __restrict__ ew, int q) {
+  if constexpr (FW) return (float)ew[q];
+  else return (float)edge_w(ex);
 }
 
 // sum_j w_ij * S[j][16c + 4(l>>4) + 0..3] over the CSR row (S: LDS rows of the block, stride LDH)
+template <bool FW = false>
 __device__ __forceinline__ void gather_ri(const RowInfo& ri, const uint32_t* __restrict__ edges, const float* S,
-                                          int rbase, int s4, float4 (&acc)[4]) {
-  for_edges(edges, ri.e0, ri.e1, [&](uint32_t ex) {
-    const float wv = (float)edge_w(ex);
+                                          int rbase, int s4, float4 (&acc)[4],
+                                          const double* __restrict__ ew = nullptr) {
+  for_edges(edges, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+    const float wv = edge_wf<FW>(ex, ew, q);
     const float* hr = S + (rbase + edge_col(ex)) * LDH + 4 * s4;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {

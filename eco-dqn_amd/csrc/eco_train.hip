@@ -752,6 +752,9 @@ extern "C" int eco_replay_sample(const eco_replay* rb, int32_t size, int32_t m, 
 static int compact_check(const eco_env_config* cfg, int32_t batch, int32_t capacity) {
   if (!cfg) return fail(ECO_ERR_ARG, "null config");
   if (cfg->optimisation_target != ECO_TARGET_CUT) return fail(ECO_ERR_TARGET, "compact replay: OptimisationTarget.CUT only");
+  if (cfg->float_weights)
+    return fail(ECO_ERR_ARG, "compact replay: integer weights only (its local field is an int16); a float-weighted "
+                             "env uses the feature ring (eco_replay_push / eco_replay_sample)");
   if (cfg->max_steps > 32767) return fail(ECO_ERR_ARG, "compact replay: max_steps must be < 32768");
   if (cfg->n_spins < 1 || cfg->n_spins > ECO_COMPACT_MAX_SPINS) return fail(ECO_ERR_ARG, "compact replay: n_spins out of range");
   if (batch < 1 || capacity < 1) return fail(ECO_ERR_ARG, "bad batch/capacity");
@@ -802,6 +805,7 @@ extern "C" int eco_replay_compact_sample(const eco_env_config* cfg, const void* 
   if (size < m || m < 1 || size > capacity || pushed < size)
     return fail(ECO_ERR_ARG, "replay sample: need m <= size <= min(capacity, pushed) (random.sample without replacement)");
   if (gs->n_spins != cfg->n_spins) return fail(ECO_ERR_ARG, "replay sample: graph set / env size mismatch");
+  if (gs->edge_weights) return fail(ECO_ERR_ARG, "compact replay: integer weights only (float-weighted graph set)");
   const EnvLayout L = env_layout(cfg->n_spins, cfg->max_steps, env_batch);
   const double* tab = (const double*)((const uint8_t*)env_state + L.off_tab + 256);
   const long long P = (long long)capacity + env_batch;

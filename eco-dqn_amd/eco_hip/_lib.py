@@ -32,6 +32,7 @@ ECO_MAX_SPINS = 2048
 ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS)
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
 ECO_GRAPH_ER, ECO_GRAPH_BA = 1, 2
+ECO_WEIGHTS_UNIFORM, ECO_WEIGHTS_DISCRETE, ECO_WEIGHTS_RANDOM = 0, 1, 2   # eco_graphs_generate weight kinds
 # kernel-path policy bits (eco_set_kernel_paths)
 ECO_PATH_NO_DENSE, ECO_PATH_NO_DL, ECO_PATH_NO_SHARED, ECO_PATH_NO_PAIR, ECO_PATH_DENSE2_FWD = 1, 2, 4, 8, 16
 
@@ -44,14 +45,15 @@ class EnvConfig(ctypes.Structure):
                 ("has_basin_reward", ctypes.c_int32), ("has_stag_punishment", ctypes.c_int32),
                 ("horizon_length", ctypes.c_int32), ("optimisation_target", ctypes.c_int32),
                 ("basin_reward", ctypes.c_double),
-                ("stag_punishment", ctypes.c_double)]
+                ("stag_punishment", ctypes.c_double), ("float_weights", ctypes.c_int32)]
 
 
 class GraphSet(ctypes.Structure):
     _fields_ = [("n_graphs", ctypes.c_int32), ("n_spins", ctypes.c_int32), ("row_ptr", ctypes.c_void_p),
                 ("edge_base", ctypes.c_void_p), ("edges", ctypes.c_void_p), ("deg", ctypes.c_void_p),
                 ("max_deg", ctypes.c_void_p), ("meta", ctypes.c_void_p), ("valid", ctypes.c_void_p),
-                ("unit_weights", ctypes.c_int32), ("adjbits", ctypes.c_void_p)]
+                ("unit_weights", ctypes.c_int32), ("adjbits", ctypes.c_void_p),
+                ("edge_weights", ctypes.c_void_p)]
 
 
 class Replay(ctypes.Structure):

@@ -122,12 +122,12 @@ class DQN:
         self.N = envs.n_spins
         self.M = int(train_minibatch or minibatch_size)
         # compact replay (one integer env state per transition, 4 B per vertex) for MaxCut envs on +-1
-        # graphs; else fp32 features
+        # graphs; else fp32 features (always for a float-weighted store: the ring's local field is an int16)
         eligible = (envs.cfg.optimisation_target == _lib.ECO_TARGET_CUT and envs.graphs.unit_weights
-                    and envs.max_steps < 32768 and self.N <= _lib.ECO_COMPACT_MAX_SPINS)
+                    and not envs.graphs.float_weights and envs.max_steps < 32768 and self.N <= _lib.ECO_COMPACT_MAX_SPINS)
         self.compact_replay = eligible if compact_replay is None else bool(compact_replay)
         if self.compact_replay and not eligible:
-            raise ValueError("compact replay needs OptimisationTarget.CUT, +-1 weights, max_steps < 32768 and "
+            raise ValueError("compact replay needs OptimisationTarget.CUT, +-1 (integer) weights, max_steps < 32768 and "
                              f"n_spins <= {_lib.ECO_COMPACT_MAX_SPINS}")
         if self.compact_replay:
             self.replay_buffer = CompactReplayBuffer(replay_buffer_size, envs, seed=self.seed)
@@ -326,7 +326,8 @@ class DQN:
             out[episodes] = ids
             return out
         kind, param = self.regenerate_graphs[:2]
-        weights = self.regenerate_graphs[2] if len(self.regenerate_graphs) > 2 else "discrete"
+        weights = (self.regenerate_graphs[2] if len(self.regenerate_graphs) > 2
+                   else "random" if self.graphs.float_weights else "discrete")
         n_slots = len(self._slot_users)
         if self._started:   # release the slots of the episodes being reset (host mirror: no device read)
             old = self._host_graph_ids

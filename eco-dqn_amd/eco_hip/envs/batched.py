@@ -20,8 +20,9 @@ def make_config(n_spins, max_steps, observables=DEFAULT_OBSERVABLES, reward_sign
                 extra_action=ExtraAction.PASS, optimisation_target=OptimisationTarget.ENERGY,
                 spin_basis=SpinBasis.SIGNED, norm_rewards=False, memory_length=None, horizon_length=None,
                 stag_punishment=None, basin_reward=None, reversible_spins=True, stopping=Stopping.NORMAL,
-                **_ignored):
-    """env_args (spinsystem.py:29-48 defaults) -> eco_env_config."""
+                float_weights=False, **_ignored):
+    """env_args (spinsystem.py:29-48 defaults) -> eco_env_config.  float_weights: the env runs a float-weighted
+    GraphStore (EdgeType.RANDOM; f64 local field, OptimisationTarget.CUT only)."""
     if optimisation_target == OptimisationTarget.ENERGY:
         # the reference factory has no ENERGY branch (score_solver.py:866-885)
         raise NotImplementedError(f"Invalid optimization target: {optimisation_target} and biased False")
@@ -42,6 +43,9 @@ def make_config(n_spins, max_steps, observables=DEFAULT_OBSERVABLES, reward_sign
                         "with a cut target)")
     if spin_basis not in (SpinBasis.SIGNED, SpinBasis.BINARY):
         raise Exception("Unrecognised SpinBasis")
+    if float_weights and optimisation_target != OptimisationTarget.CUT:
+        raise ValueError(f"float edge weights (EdgeType.RANDOM) run OptimisationTarget.CUT only, not "
+                         f"{optimisation_target}: the generic-scorer kernels are integer")
     c = _lib.EnvConfig()
     c.n_spins = n_spins
     c.max_steps = max_steps
@@ -59,6 +63,7 @@ def make_config(n_spins, max_steps, observables=DEFAULT_OBSERVABLES, reward_sign
     c.stag_punishment = float(stag_punishment) if stag_punishment is not None else 0.0
     c.horizon_length = int(horizon_length if horizon_length is not None else max_steps)
     c.optimisation_target = optimisation_target.value
+    c.float_weights = int(bool(float_weights))
     return c
 
 
@@ -76,7 +81,9 @@ class VecSpinSystem:
         self.n_spins = graphs.n_spins
         self.max_steps = max_steps
         self.env_args = env_args
-        self.cfg = make_config(graphs.n_spins, max_steps, **env_args)
+        env_args = dict(env_args)
+        env_args.pop("float_weights", None)   # the store decides
+        self.cfg = make_config(graphs.n_spins, max_steps, float_weights=graphs.float_weights, **env_args)
         self.n_obs = self.cfg.n_obs
         self.reversible_spins = bool(self.cfg.reversible_spins)
         self.spin_basis = env_args.get("spin_basis", SpinBasis.SIGNED)

@@ -132,7 +132,9 @@ class SpinSystemBase:
         key = id(matrix)
         if key != self._matrix_key or self._vec is None:
             store = GraphStore.from_dense([np.asarray(matrix, dtype=np.float64)], device=self.device)
-            if self._vec is None:
+            if self._vec is None or store.float_weights != self._vec.graphs.float_weights:
+                # (a generator that switches between integer and float weights gets a fresh state buffer: the
+                # resident local field changes type)
                 self._vec = VecSpinSystem(store, 1, self.max_steps, want_f64=True, **self._env_args)
             else:  # same episode state: the scorer's normalisers carry over like the reference's (:216-219)
                 self._vec.graphs = store

@@ -99,7 +99,6 @@ def _edge_weights(edge_type, size):
     if edge_type == EdgeType.DISCRETE:
         return 2.0 * np.random.randint(2, size=size) - 1.0
     if edge_type == EdgeType.RANDOM:
-        # accepted by the generator; the HIP engine takes integer weights only
         return 2.0 * np.random.rand(size) - 1.0
     raise NotImplementedError()
 

@@ -24,18 +24,22 @@ Graph = namedtuple('Graph', 'name n_vertices n_edges matrix bk_val bk_sol')
 
 def read_mc(path):
     """GSet / MaxCut `.mc` instance (experiments/utils.py:400-409): first line `n m`, then `i j w` per edge,
-    1-based.  Returns (n, m, i, j, w) with 0-based endpoints."""
+    1-based.  Returns (n, m, i, j, w) with 0-based endpoints; w is int64 when every weight is an integer, else
+    float64 (a real-weighted instance: GraphStore.from_edges then builds a float-weighted store)."""
     with open(path) as f:
         head = f.readline().split()
         if len(head) != 2:
             raise ValueError("First line in file should define graph dimensions.")
         n, m = int(head[0]), int(head[1])
-        rows = np.loadtxt(f, dtype=np.int64, ndmin=2)
+        rows = np.loadtxt(f, dtype=np.float64, ndmin=2)
     if rows.size == 0:
-        rows = np.zeros((0, 3), np.int64)
+        rows = np.zeros((0, 3), np.float64)
     if rows.shape[1] != 3:
         raise ValueError("edge lines must be `i j w`")
-    return n, m, rows[:, 0] - 1, rows[:, 1] - 1, rows[:, 2]
+    w = rows[:, 2]
+    if np.all(w == np.round(w)):
+        w = w.astype(np.int64)
+    return n, m, rows[:, 0].astype(np.int64) - 1, rows[:, 1].astype(np.int64) - 1, w
 
 
 def load_graph(graph_dir, graph_name, dense=True):

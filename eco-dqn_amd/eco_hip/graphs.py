@@ -2,7 +2,9 @@
 
 Replaces the dense `GraphGenerator.get() -> ndarray[N,N] f64` adjacency that the
 reference stacks under every observation (spinsystem.py:561-574): on the device a
-graph is CSR with integer weights, shared by every episode that references its id.
+graph is CSR, shared by every episode that references its id: integer weights in [-128, 127] packed into
+the edge word, or (EdgeType.RANDOM, any other weight) a parallel float64 weights array with the weight's sign
+in the word.
 Host-side construction is numpy (input preparation, not the hot path); the
 normalisers (mlr, qn, lb, degrees) are computed on the device by
 eco_graphs_prepare.
@@ -15,17 +17,48 @@ import torch
 from . import _lib
 
 
-def _pack_edges(cols, weights):
+def _is_float_weights(weights):
+    """True when the weights need the float64 path: any non-integer value or one outside [-128, 127]
+    (EdgeType.RANDOM, src/envs/utils.py:137-148,323-330)."""
     w = np.asarray(weights)
-    if not np.all(np.equal(np.mod(w, 1), 0)) or w.min(initial=0) < -128 or w.max(initial=0) > 127:
-        raise ValueError("eco_hip graphs take integer edge weights in [-128, 127] "
-                         "(EdgeType.UNIFORM / DISCRETE); EdgeType.RANDOM is not supported on the device")
+    return bool(w.size) and (not np.all(np.equal(np.mod(w, 1), 0)) or w.min() < -128 or w.max() > 127)
+
+
+def _pack_edges(cols, weights, as_float=False):
+    """Packed edge words column | (uint8 weight << 24).  as_float: the byte holds sign(w) (the float64 weights
+    travel in a parallel array)."""
+    w = np.asarray(weights)
+    if as_float:
+        w = np.sign(w)
+    elif _is_float_weights(w):
+        raise ValueError("non-integer edge weights need the float-weights path (as_float=True)")
     return (np.asarray(cols, dtype=np.uint32) | ((w.astype(np.int64) & 0xFF).astype(np.uint32) << 24)).astype(np.uint32)
 
 
+class CSR(tuple):
+    """(row_ptr, edge_base, edges) with the float64 weights of a float-weighted set in `.weights` (None for
+    integer weights).  An integer CSR is a plain 3-tuple to every caller that unpacks it.  A float-weighted one
+    refuses to be unpacked or iterated (indexing still works): `GraphStore(*csr)` or `tuple(csr)` would drop the
+    weights and leave an integer graph of their signs.  Build a store with GraphStore.from_csr(csr)."""
+
+    def __new__(cls, row_ptr, edge_base, edges, weights=None):
+        t = super().__new__(cls, (row_ptr, edge_base, edges))
+        t.weights = weights
+        return t
+
+    def __iter__(self):
+        if self.weights is not None:
+            raise TypeError("a float-weighted CSR cannot be unpacked into (row_ptr, edge_base, edges): its weights "
+                            "would be lost; use GraphStore.from_csr(csr), or csr[0..2] and csr.weights")
+        return super().__iter__()
+
+
 def dense_to_csr(matrices):
-    """list of [N,N] symmetric zero-diagonal matrices -> (row_ptr [G][N+1], edge_base [G], edges)."""
+    """list of [N,N] symmetric zero-diagonal matrices -> CSR (row_ptr [G][N+1], edge_base [G], edges); float
+    weights (any non-integer or outside [-128, 127], in any matrix) also give .weights [total edges] f64."""
     mats = [np.asarray(m) for m in matrices]
+    fw = any(_is_float_weights(m) for m in mats)
+    wchunks = []
     n = mats[0].shape[0]
     row_ptr = np.zeros((len(mats), n + 1), dtype=np.int32)
     bases = np.zeros(len(mats), dtype=np.int64)
@@ -41,17 +74,23 @@ def dense_to_csr(matrices):
         r, c = np.nonzero(m)
         row_ptr[g, 1:] = np.cumsum(np.bincount(r, minlength=n))
         bases[g] = off
-        chunks.append(_pack_edges(c, m[r, c]))
+        chunks.append(_pack_edges(c, m[r, c], fw))
+        if fw:
+            wchunks.append(np.asarray(m[r, c], dtype=np.float64))
         off += r.size
     edges = np.concatenate(chunks) if chunks else np.zeros(0, np.uint32)
-    return row_ptr, bases, edges
+    return CSR(row_ptr, bases, edges, np.concatenate(wchunks) if fw else None)
 
 
 def edges_to_csr(n, i, j, w):
-    """One graph from an undirected edge list (each edge once, 0-based) -> (row_ptr [1][N+1], edge_base [1],
+    """One graph from an undirected edge list (each edge once, 0-based) -> CSR (row_ptr [1][N+1], edge_base [1],
     edges): the CSR of the symmetric matrix load_graph builds (matrix[[i,j],[j,i]] = w), without the dense
-    N x N array (GSet graphs, N = 800 .. 20,000).  A repeated pair keeps its last weight, as the reference."""
-    i, j, w = (np.asarray(v, dtype=np.int64) for v in (i, j, w))
+    N x N array (GSet graphs, N = 800 .. 20,000).  A repeated pair keeps its last weight, as the reference.
+    Real-valued weights (or integers outside [-128, 127]) give a float-weighted CSR (.weights)."""
+    i, j = (np.asarray(v, dtype=np.int64) for v in (i, j))
+    w = np.asarray(w)
+    fw = _is_float_weights(w)
+    w = w.astype(np.float64) if fw else w.astype(np.int64)
     if i.size and (min(i.min(), j.min()) < 0 or max(i.max(), j.max()) >= n):
         raise ValueError("edge endpoint out of range")
     if np.any(i == j):
@@ -69,14 +108,17 @@ def edges_to_csr(n, i, j, w):
     r, c, ww = r[order], c[order], ww[order]
     row_ptr = np.zeros((1, n + 1), dtype=np.int32)
     row_ptr[0, 1:] = np.cumsum(np.bincount(r, minlength=n))
-    return row_ptr, np.zeros(1, dtype=np.int64), _pack_edges(c, ww)
+    return CSR(row_ptr, np.zeros(1, dtype=np.int64), _pack_edges(c, ww, fw), ww if fw else None)
 
 
 def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512):
     """Seeded synthetic graph pool built directly as CSR (no dense N x N per graph).
     kind 'ER': G(n, p=param); 'BA': preferential attachment with m=param.
-    weights 'discrete' = fair +-1 per edge (EdgeType.DISCRETE), 'uniform' = 1."""
+    weights 'discrete' = fair +-1 per edge (EdgeType.DISCRETE), 'uniform' = 1, 'random' = float64 uniform in
+    (-1, 1) (EdgeType.RANDOM; a float-weighted CSR with .weights)."""
     rng = np.random.default_rng(seed)
+    fw = weights == "random"
+    wparts = []
     row_ptr = np.zeros((n_graphs, n + 1), dtype=np.int32)
     bases = np.zeros(n_graphs, dtype=np.int64)
     parts = []
@@ -92,7 +134,11 @@ def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512):
                 iu, ju = _ba_edges(n, int(param), rng)
             else:
                 raise ValueError(kind)
-            w = (2 * rng.integers(0, 2, iu.size) - 1) if weights == "discrete" else np.ones(iu.size, np.int64)
+            if fw:
+                w = rng.uniform(-1.0, 1.0, iu.size)
+                w[w == 0.0] = 2.0 ** -53   # stored weights are nonzero
+            else:
+                w = (2 * rng.integers(0, 2, iu.size) - 1) if weights == "discrete" else np.ones(iu.size, np.int64)
             r = np.concatenate([iu, ju])
             c = np.concatenate([ju, iu])
             ww = np.concatenate([w, w])
@@ -100,9 +146,11 @@ def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512):
             r, c, ww = r[order], c[order], ww[order]
             row_ptr[g, 1:] = np.cumsum(np.bincount(r, minlength=n))
             bases[g] = off
-            parts.append(_pack_edges(c, ww))
+            parts.append(_pack_edges(c, ww, fw))
+            if fw:
+                wparts.append(ww)
             off += r.size
-    return row_ptr, bases, np.concatenate(parts)
+    return CSR(row_ptr, bases, np.concatenate(parts), np.concatenate(wparts) if fw else None)
 
 
 def _ba_edges(n, m, rng):
@@ -132,11 +180,26 @@ def edge_cap(kind, n, param, slack_sd=10.0):
 
 
 class GraphStore:
-    """G graphs of N vertices resident on the device (eco_graph_set)."""
+    """G graphs of N vertices resident on the device (eco_graph_set).  edge_weights: float64 [total edges]
+    parallel to `edges` for a float-weighted store (EdgeType.RANDOM), None for integer weights; a store holds one
+    kind (`float_weights`)."""
 
-    def __init__(self, row_ptr, edge_base, edges, device="cuda", stream=None, unit_weights=None):
+    def __init__(self, row_ptr, edge_base, edges, device="cuda", stream=None, unit_weights=None,
+                 edge_weights=None):
         dev = torch.device(device)
         self.device = dev
+        self.float_weights = edge_weights is not None
+        if self.float_weights:
+            if unit_weights:
+                raise ValueError("a float-weighted store cannot have unit_weights")
+            unit_weights = False
+            if isinstance(edge_weights, torch.Tensor):
+                self.edge_weights = edge_weights
+            else:
+                ew = np.ascontiguousarray(edge_weights, dtype=np.float64)
+                self.edge_weights = torch.from_numpy(ew if ew.size else np.zeros(1, np.float64)).to(dev)
+        else:
+            self.edge_weights = None
         if isinstance(row_ptr, torch.Tensor):
             self.row_ptr, self.edge_base, self.edges = row_ptr, edge_base, edges
             self.n_graphs, n1 = row_ptr.shape
@@ -164,24 +227,30 @@ class GraphStore:
         self.gs = _lib.GraphSet(self.n_graphs, self.n_spins, self.row_ptr.data_ptr(), self.edge_base.data_ptr(),
                                 self.edges.data_ptr(), self.deg.data_ptr(), self.max_deg.data_ptr(),
                                 self.meta.data_ptr(), self.valid.data_ptr(), int(self.unit_weights),
-                                self.adjbits.data_ptr() if nb else None)
+                                self.adjbits.data_ptr() if nb else None,
+                                self.edge_weights.data_ptr() if self.float_weights else None)
         _lib.check(_lib.lib.eco_graphs_prepare(ctypes.byref(self.gs), _lib.stream_ptr(stream)))
 
     @classmethod
-    def slots(cls, n_graphs, n, cap, device="cuda"):
-        """Empty store with fixed edge slots (edge_base[g] = g * cap) for eco_graphs_generate."""
+    def slots(cls, n_graphs, n, cap, device="cuda", weights="discrete"):
+        """Empty store with fixed edge slots (edge_base[g] = g * cap) for eco_graphs_generate;
+        weights="random": a float-weighted store (float64 weight slots next to the edge words)."""
         dev = torch.device(device)
         rp = torch.zeros(n_graphs, n + 1, dtype=torch.int32, device=dev)
         eb = torch.arange(n_graphs, dtype=torch.int64, device=dev) * int(cap)
         ed = torch.zeros(max(1, n_graphs * int(cap)), dtype=torch.int32, device=dev)
-        st = cls(rp, eb, ed, device=dev, unit_weights=True)  # eco_graphs_generate writes +-1 / 1 weights
+        if weights == "random":
+            st = cls(rp, eb, ed, device=dev,
+                     edge_weights=torch.zeros(max(1, n_graphs * int(cap)), dtype=torch.float64, device=dev))
+        else:
+            st = cls(rp, eb, ed, device=dev, unit_weights=True)  # eco_graphs_generate writes +-1 / 1 weights
         st.cap = int(cap)
         return st
 
     @classmethod
     def generated(cls, kind, n_graphs, n, param, seed=0, weights="discrete", device="cuda"):
         """Pool of n_graphs ER(n, p=param) / BA(n, m=param) graphs generated on the device."""
-        st = cls.slots(n_graphs, n, edge_cap(kind, n, param), device=device)
+        st = cls.slots(n_graphs, n, edge_cap(kind, n, param), device=device, weights=weights)
         st.generate(0, n_graphs, kind, param, seed, weights)
         return st
 
@@ -193,8 +262,13 @@ class GraphStore:
         ws = torch.empty(_lib.lib.eco_graphs_generate_workspace_bytes(self.n_spins, count), dtype=torch.uint8,
                          device=self.device)
         k = {"ER": _lib.ECO_GRAPH_ER, "BA": _lib.ECO_GRAPH_BA}[kind]
+        wk = {"uniform": _lib.ECO_WEIGHTS_UNIFORM, "discrete": _lib.ECO_WEIGHTS_DISCRETE,
+              "random": _lib.ECO_WEIGHTS_RANDOM}[weights]
+        if (weights == "random") != self.float_weights:
+            raise ValueError("a store holds one weight kind: weights='random' needs a store made with "
+                             "weights='random', and the integer kinds one made without")
         _lib.check(_lib.lib.eco_graphs_generate(ctypes.byref(self.gs), first, count, k, float(param),
-                                                int(weights == "discrete"), ctypes.c_uint64(seed), self.cap,
+                                                wk, ctypes.c_uint64(seed), self.cap,
                                                 _lib.ptr(ws), _lib.stream_ptr(stream)))
         if check:  # an edge-slot overflow leaves an empty graph and sets the device error word
             self.check_errors(stream)
@@ -204,24 +278,33 @@ class GraphStore:
         _lib.check(_lib.lib.eco_check_errors(_lib.stream_ptr(stream)))
 
     @classmethod
+    def from_csr(cls, csr, device="cuda"):
+        """Store from a CSR of dense_to_csr / edges_to_csr / random_csr, float weights included."""
+        return cls(csr[0], csr[1], csr[2], device=device, edge_weights=csr.weights)
+
+    @classmethod
     def from_dense(cls, matrices, device="cuda"):
-        return cls(*dense_to_csr(matrices), device=device)
+        return cls.from_csr(dense_to_csr(matrices), device=device)
 
     @classmethod
     def from_edges(cls, n, i, j, w, device="cuda"):
         """Single-graph store from an undirected edge list (GSet .mc instances, load_gset)."""
-        return cls(*edges_to_csr(n, i, j, w), device=device)
+        return cls.from_csr(edges_to_csr(n, i, j, w), device=device)
 
     @classmethod
     def random(cls, kind, n_graphs, n, param, seed=0, weights="discrete", device="cuda"):
-        return cls(*random_csr(kind, n_graphs, n, param, seed, weights), device=device)
+        return cls.from_csr(random_csr(kind, n_graphs, n, param, seed, weights), device=device)
 
     def dense(self, g):
-        """Host dense adjacency of graph g (for the reference-format observation)."""
+        """Host dense adjacency of graph g (for the reference-format observation); the float64 weights of a
+        float-weighted store."""
         rp = self.row_ptr[g].cpu().numpy()
         b = int(self.edge_base[g].item())
         e = self.edges[b:b + int(rp[-1])].cpu().numpy().view(np.uint32)
         m = np.zeros((self.n_spins, self.n_spins))
         rows = np.repeat(np.arange(self.n_spins), np.diff(rp))
-        m[rows, e & 0xFFFFFF] = ((e >> 24).astype(np.uint8)).view(np.int8)
+        if self.float_weights:
+            m[rows, e & 0xFFFFFF] = self.edge_weights[b:b + int(rp[-1])].cpu().numpy()
+        else:
+            m[rows, e & 0xFFFFFF] = ((e >> 24).astype(np.uint8)).view(np.int8)
         return m

@@ -209,7 +209,7 @@ class MPNN(torch.nn.Module):
         x = torch.zeros(B, N, _lib.obs_x_stride(k), dtype=torch.float32, device=self.flat.device)
         x[:, :, :k] = view[:, :k, :].transpose(1, 2).to(x.device, torch.float32)
         adj = view[:, k:, :].detach().cpu().numpy()
-        store = GraphStore(*dense_to_csr([a.T for a in adj]), device=self.flat.device)
+        store = GraphStore.from_csr(dense_to_csr([a.T for a in adj]), device=self.flat.device)
         gids = torch.arange(B, dtype=torch.int32, device=self.flat.device)
         q = self.forward_graphs(x, store, gids, norm_scope=_lib.ECO_NORM_PER_CALL)
         if obs.dim() == 3:

@@ -88,6 +88,12 @@ typedef struct {
   int32_t optimisation_target;    /* ECO_TARGET_* */
   double basin_reward;
   double stag_punishment;
+  int32_t float_weights;          /* 1: the env runs a float-weighted graph set (gs->edge_weights != NULL,
+                                     EdgeType.RANDOM): the resident local field is f64 (8 B per vertex of the state
+                                     buffer instead of 4) and the CUT kernels' float64 instantiations run.  0
+                                     (default): integer weights, the state layout of every earlier version.
+                                     OptimisationTarget.CUT only; eco_env_reset / eco_env_step return ECO_ERR_ARG
+                                     when the flag disagrees with the graph set. */
 } eco_env_config;
 
 /* A set of G graphs with N vertices each, as CSR on the device.
@@ -100,7 +106,9 @@ typedef struct {
   int32_t n_spins;
   const int32_t *row_ptr;   /* [G][N+1] edge offsets local to each graph */
   const int64_t *edge_base; /* [G] offset of graph g's first edge in `edges` */
-  const uint32_t *edges;    /* packed edge: column | ((uint8_t)weight << 24); integer weights in [-128,127] */
+  const uint32_t *edges;    /* packed edge: column | ((uint8_t)weight << 24); integer weights in [-128,127], or
+                               sign(w) (+1 / -1) in a float-weighted set (edge_weights != NULL), so the nonzero
+                               counts (deg, max_deg) read the same words either way */
   int32_t *deg;             /* [G][N] number of nonzero entries per row (mpnn.py:34-38, before the 0->1 clamp) */
   int32_t *max_deg;         /* [G] max over rows of max(deg,1) */
   double *meta;             /* [G][4]: max_local_reward, quality_normalizer, lower_bound, sum(J) */
@@ -112,10 +120,20 @@ typedef struct {
                                per graph, node and lane quarter the bitmask adjacency operand of the dense MPNN
                                kernels ([G][N][4][4] u32 up to N = 224, [G][N][4][8] above, to N = 512), so
                                they skip the per-call CSR -> bitmask build */
+  const double *edge_weights; /* NULL: integer weights (the packed byte).  Otherwise [total edges] float64 weights
+                               parallel to `edges` (EdgeType.RANDOM, src/envs/utils.py:137-148: the reference's
+                               adjacency is float64); zero weights are not stored.  Needs unit_weights == 0
+                               (ECO_ERR_ARG otherwise).  A float-weighted set runs OptimisationTarget.CUT envs
+                               (cfg.float_weights = 1) and the CSR-gather MPNN kernels, which read (float)w as the
+                               reference's obs.float() does (dqn.py:282); the dense, shared-graph and fused-pair
+                               MPNN kernels, the generic-scorer targets and the compact replay ring are
+                               integer-only and reject it with ECO_ERR_ARG before any launch. */
 } eco_graph_set;
 
 /* Graph metadata: MaximumCutUnbiasedScorer normalisers (score_solver.py:347-375)
- * and the MPNN degree normalisation (mpnn.py:34-38), computed on the device. */
+ * and the MPNN degree normalisation (mpnn.py:34-38), computed on the device.  Float-weighted sets: float64
+ * row sums, one lane per row in CSR order, then fixed-order wave and workgroup reductions (no floating-point
+ * atomics): bitwise reproducible run to run. */
 int eco_graphs_prepare(eco_graph_set *gs, eco_stream_t stream);
 
 /* Bytes of gs->adjbits for G graphs of N vertices: nonzero only where the dense MPNN path runs one graph
@@ -125,18 +143,23 @@ size_t eco_graphs_adjbits_bytes(int32_t n_spins, int32_t n_graphs);
 /* On-device graph generation into graphs [first, first+count) of a set whose edge slots are
  * fixed (edge_base[g] = g * edge_cap): the training-reset graph draws of
  * RandomErdosRenyiGraphGenerator (kind ER, param = p) and RandomBarabasiAlbertGraphGenerator
- * (kind BA, param = m) (src/envs/utils.py:165-236); +-1 weights when discrete_weights, else 1.
+ * (kind BA, param = m) (src/envs/utils.py:165-236).  weight_kind: ECO_WEIGHTS_UNIFORM = every weight 1,
+ * ECO_WEIGHTS_DISCRETE = fair +-1, ECO_WEIGHTS_RANDOM = float64 uniform in (-1, 1) (EdgeType.RANDOM,
+ * utils.py:137-148): w = 2u - 1 with u a 53-bit draw of the counter generator keyed by (seed, graph, unordered
+ * pair), so the matrix is symmetric by construction; needs gs->edge_weights (written like `edges`), and the
+ * packed byte holds sign(w).
  * Runs eco_graphs_prepare afterwards.  An edge-slot overflow is reported by eco_check_errors. */
 enum { ECO_GRAPH_ER = 1, ECO_GRAPH_BA = 2 };
+enum { ECO_WEIGHTS_UNIFORM = 0, ECO_WEIGHTS_DISCRETE = 1, ECO_WEIGHTS_RANDOM = 2 };
 size_t eco_graphs_generate_workspace_bytes(int32_t n_spins, int32_t count);
 int eco_graphs_generate(eco_graph_set *gs, int32_t first, int32_t count, int32_t kind, double param,
-                        int32_t discrete_weights, uint64_t seed, int64_t edge_cap, void *workspace,
+                        int32_t weight_kind, uint64_t seed, int64_t edge_cap, void *workspace,
                         eco_stream_t stream);
 
 /* ---- batched SpinSystem (spinsystem.py) ---- */
 
 /* Bytes of the opaque per-batch env state buffer (spins, local fields, counters,
- * best-so-far, visited-state sets). */
+ * best-so-far, visited-state sets).  A pure query of cfg (float_weights included) and batch. */
 size_t eco_env_state_bytes(const eco_env_config *cfg, int32_t batch);
 
 /* SpinSystemBase.reset (spinsystem.py:183-259, _reset_state :283-330).
@@ -320,7 +343,8 @@ int eco_replay_sample(const eco_replay *rb, int32_t size, int32_t m, uint64_t se
  * (J s)_v as int16} -- plus four float64 observation scalars for s and for s' and graph id / action /
  * reward / done: 4N + 80 bytes per transition.  s' is rebuilt on sample from s, the action and the graph
  * (the env's step), and both states' feature rows are rebuilt with the env's own observation arithmetic
- * (spinsystem.py:486-535), bit-exactly.  Same ReplayBuffer semantics: the newest `capacity` transitions
+ * (spinsystem.py:486-535), bit-exactly.  Integer weights only: a float-weighted env or graph set is rejected
+ * with ECO_ERR_ARG (the local field would not fit an int16; use the eco_replay feature ring).  Same ReplayBuffer semantics: the newest `capacity` transitions
  * are held, sample = m distinct uniform ones (random.sample, :53).  `pushed` counts the transitions added
  * over the buffer's life (the k-th lives in slot k % (capacity + batch)); push writes each episode's s'
  * straight into the slot of its next transition, so `ring` (caller-owned device memory of
