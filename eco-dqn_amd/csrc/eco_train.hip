@@ -1,7 +1,7 @@
 // DQN training hot path on gfx950 (src/agents/dqn/dqn.py:403-451, dqn/utils.py:28-83):
-// device replay ring, double-DQN TD target + MSE gradient, MPNN weight gradients
+// device replay ring, double-DQN TD target + MSE / Huber gradient, MPNN weight gradients
 // (split-K reductions over every node of the minibatch on bf16x3-split v_mfma_f32_32x32x16_bf16,
-// per-wave partial slabs reduced in a fixed order -> bitwise reproducible), Adam.
+// per-wave partial slabs reduced in a fixed order -> bitwise reproducible), gradient-norm clipping, Adam.
 #include <cmath>
 
 #include "eco_mpnn.h"
@@ -288,6 +288,10 @@ __global__ void colsum_jobs_kernel(ColJobs jobs) {
 // td = r + (1 - done) * gamma * q_t, loss = mean((q(s,a) - td)^2), dq = dloss/dq.
 // One thread per element of dq[B][N]: the element of the taken action gets the TD gradient (and its row's
 // squared error), every other element zero -- the zero-fill of loss.backward()'s dQ and the TD step in one pass.
+// HUBER: smooth_l1_loss(beta = 1) instead of mse_loss (dqn.py:172): per-sample loss 0.5 d^2 for |d| < 1, else
+// |d| - 0.5; gradient d / B clamped to +-1 / B.  The comparisons are torch's own (x < -beta, x > beta, else
+// x), so a NaN d stays NaN in dq and in the loss.
+template <bool HUBER>
 __global__ void td_kernel(const float* q_s, const float* q_tn, const int32_t* a_star, const int32_t* actions,
                           const float* rewards, const float* dones, int B, int N, float gamma, int clip,
                           float* dq, float* sqerr) {
@@ -307,8 +311,14 @@ __global__ void td_kernel(const float* q_s, const float* q_tn, const int32_t* a_
   const float td = rewards[b] + (1.f - dones[b]) * gamma * qt;
   const float q = q_s[i];
   const float diff = q - td;
-  dq[i] = 2.f * diff / (float)B;  // mse_loss(reduction='mean') backward
-  sqerr[b] = diff * diff;
+  if (HUBER) {
+    const float ad = fabsf(diff);
+    dq[i] = (diff < -1.f ? -1.f : diff > 1.f ? 1.f : diff) / (float)B;  // smooth_l1_loss(reduction='mean') backward
+    sqerr[b] = ad < 1.f ? 0.5f * diff * diff : ad - 0.5f;
+  } else {
+    dq[i] = 2.f * diff / (float)B;  // mse_loss(reduction='mean') backward
+    sqerr[b] = diff * diff;
+  }
 }
 
 __global__ void mean_kernel(const float* v, int n, float* out) {
@@ -339,6 +349,60 @@ __global__ void adam_kernel(float* p, const float* g, float* m, float* v, int n,
   v[i] = vi;
   const float denom = sqrtf(vi) / bc2_sqrt + eps;
   p[i] = p[i] - step_size * (mi / denom);
+}
+
+// --------------------------------------------------------------- grad clip ----
+// torch.nn.utils.clip_grad_norm_(parameters, max_norm), norm type 2, over the flat gradient (dqn.py:446-447).
+// Three launches, no atomics and no host read: (1) each workgroup sums g^2 over its chunks of GC_CHUNK elements
+// in float64 (per thread in index order, then the wave butterfly, then the four waves in order) into its slot of
+// the library's partial buffer; (2) one workgroup sums the partials the same way and writes {total_norm, coef};
+// (3) grad *= coef.  The grid depends on n alone, so the result is bitwise reproducible run to run.
+constexpr int GC_CHUNK = 2048;       // elements per workgroup pass: 8 per thread
+constexpr int GC_MAX_BLOCKS = 1024;  // partial slots; above GC_CHUNK * GC_MAX_BLOCKS elements workgroups take more chunks
+__device__ double g_clip_partial[GC_MAX_BLOCKS];
+
+// fixed-order sum over the 256 threads of a workgroup; the result is valid in thread 0
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, int n) {
+  __shared__ double red[4];
+  const long long nchunk = ((long long)n + GC_CHUNK - 1) / GC_CHUNK;
+  double acc = 0.0;
+  for (long long c = blockIdx.x; c < nchunk; c += gridDim.x) {
+#pragma unroll
+    for (int k = 0; k < GC_CHUNK / 256; ++k) {
+      const long long i = c * GC_CHUNK + k * 256 + threadIdx.x;
+      const double v = i < n ? (double)g[i] : 0.0;
+      acc += v * v;
+    }
+  }
+  const double s = block_sum_d(acc, red);
+  if (threadIdx.x == 0) g_clip_partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_kernel(int nblk, double grad_scale, double max_norm, float* norm_out) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < nblk; k += 256) acc += g_clip_partial[k];
+  const double s = block_sum_d(acc, red);
+  if (threadIdx.x == 0) {
+    const double total = grad_scale * sqrt(s);
+    const double c = max_norm / (total + 1e-6);
+    norm_out[0] = (float)total;
+    norm_out[1] = (float)(c > 1.0 ? 1.0 : c);  // clamp(max = 1); a NaN norm stays NaN
+  }
+}
+
+__global__ void grad_scale_kernel(float* g, int n, const float* norm_out) {
+  const float coef = norm_out[1];
+  if (coef == 1.f) return;  // x * 1.0f is x: nothing to write
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)n) g[i] *= coef;
 }
 
 // ------------------------------------------------------------------ replay ----
@@ -697,19 +761,47 @@ extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const ec
   return check_launch("mpnn_backward_wgrad");
 }
 
+extern "C" int eco_dqn_td_loss(const float* q_s, const float* q_target_next, const int32_t* a_star,
+                               const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
+                               int32_t n_spins, float gamma, int32_t clip_q_targets, int32_t loss_kind, float* dq,
+                               float* sqerr, float* loss, eco_stream_t stream) {
+  if (!q_s || !q_target_next || !a_star || !actions || !rewards || !dones || !dq || !sqerr || !loss)
+    return fail(ECO_ERR_ARG, "null argument");
+  if (batch < 1 || n_spins < 1) return fail(ECO_ERR_ARG, "bad batch/n_spins");
+  if (loss_kind != ECO_LOSS_MSE && loss_kind != ECO_LOSS_HUBER)
+    return fail(ECO_ERR_ARG, "loss_kind must be ECO_LOSS_MSE or ECO_LOSS_HUBER");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)batch * n_spins;
+  const unsigned nblk = (unsigned)((n + 255) / 256);
+  if (loss_kind == ECO_LOSS_HUBER)
+    td_kernel<true><<<nblk, 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma,
+                                          clip_q_targets, dq, sqerr);
+  else
+    td_kernel<false><<<nblk, 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma,
+                                           clip_q_targets, dq, sqerr);
+  mean_kernel<<<1, 256, 0, st>>>(sqerr, batch, loss);
+  return check_launch("dqn_td");
+}
+
 extern "C" int eco_dqn_td(const float* q_s, const float* q_target_next, const int32_t* a_star,
                           const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
                           int32_t n_spins, float gamma, int32_t clip_q_targets, float* dq, float* sqerr,
                           float* loss, eco_stream_t stream) {
-  if (!q_s || !q_target_next || !a_star || !actions || !rewards || !dones || !dq || !sqerr || !loss)
-    return fail(ECO_ERR_ARG, "null argument");
-  if (batch < 1 || n_spins < 1) return fail(ECO_ERR_ARG, "bad batch/n_spins");
+  return eco_dqn_td_loss(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma, clip_q_targets,
+                         ECO_LOSS_MSE, dq, sqerr, loss, stream);
+}
+
+extern "C" int eco_grad_clip(float* grad, int32_t n, double grad_scale, double max_norm, float* norm_out,
+                             eco_stream_t stream) {
+  if (!grad || !norm_out) return fail(ECO_ERR_ARG, "null argument");
+  if (n < 1) return fail(ECO_ERR_ARG, "grad clip: n must be positive");
+  if (!(max_norm > 0.0) || !std::isfinite(max_norm)) return fail(ECO_ERR_ARG, "grad clip: max_norm must be finite and positive");
   hipStream_t st = (hipStream_t)stream;
-  const size_t n = (size_t)batch * n_spins;
-  td_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch,
-                                                         n_spins, gamma, clip_q_targets, dq, sqerr);
-  mean_kernel<<<1, 256, 0, st>>>(sqerr, batch, loss);
-  return check_launch("dqn_td");
+  const int nblk = (int)std::min<long long>(GC_MAX_BLOCKS, ((long long)n + GC_CHUNK - 1) / GC_CHUNK);
+  grad_sumsq_kernel<<<nblk, 256, 0, st>>>(grad, n);
+  grad_norm_kernel<<<1, 256, 0, st>>>(nblk, grad_scale, max_norm, norm_out);
+  grad_scale_kernel<<<(unsigned)(((size_t)n + 255) / 256), 256, 0, st>>>(grad, n, norm_out);
+  return check_launch("grad_clip");
 }
 
 extern "C" int eco_adam(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t n, double lr,

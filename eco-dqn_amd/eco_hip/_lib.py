@@ -33,6 +33,7 @@ ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuil
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
 ECO_GRAPH_ER, ECO_GRAPH_BA = 1, 2
 ECO_WEIGHTS_UNIFORM, ECO_WEIGHTS_DISCRETE, ECO_WEIGHTS_RANDOM = 0, 1, 2   # eco_graphs_generate weight kinds
+ECO_LOSS_MSE, ECO_LOSS_HUBER = 0, 1   # eco_dqn_td_loss loss kinds
 # kernel-path policy bits (eco_set_kernel_paths)
 ECO_PATH_NO_DENSE, ECO_PATH_NO_DL, ECO_PATH_NO_SHARED, ECO_PATH_NO_PAIR, ECO_PATH_DENSE2_FWD = 1, 2, 4, 8, 16
 
@@ -101,6 +102,8 @@ _SIG = {
     "eco_mpnn_backward_workspace_bytes": (ctypes.c_size_t, [_I, _I]),
     "eco_mpnn_backward": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P, _P, _P]),
     "eco_dqn_td": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
+    "eco_dqn_td_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
+    "eco_grad_clip": (ctypes.c_int, [_P, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
     "eco_adam": (ctypes.c_int, [_P, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, _P]),
     "eco_replay_push": (ctypes.c_int, [ctypes.POINTER(Replay), _I, _I, _P, _P, _P, _P, _P, _P, _P]),

@@ -8,7 +8,8 @@ advances B episodes.  Everything on the step path runs in libecohip:
   env.step  -> batched SpinSystem kernel (spinsystem.py:355-559)
   replay    -> device ring push / distinct-index sample (dqn/utils.py:28-83)
   train     -> online(s') argmax, target(s') gather, online(s) forward with saved
-               activations, TD + MSE gradient, MPNN backward, Adam (dqn.py:403-451)
+               activations, TD + MSE / Huber gradient, MPNN backward, optional gradient-norm clipping,
+               Adam (dqn.py:403-451)
 Schedules are per env-step as in the reference; a vector step advances the
 counter by B.  The replay ratio of the reference (minibatch_size/update_frequency
 samples per env-step, 64/32 = 2 in train_eco.py:136-137) is kept by running
@@ -18,6 +19,7 @@ and averaged inside the Adam kernel; parameters stay bit-identical across ranks.
 """
 import ctypes
 import math
+import numbers
 import os
 import random
 
@@ -54,10 +56,19 @@ class DQN:
             if len(envs) != 1:
                 raise NotImplementedError("pass one VecSpinSystem (it already holds B episodes)")
             envs = envs[0]
-        if loss != "mse":
-            raise NotImplementedError("eco_hip implements the reference's training loss 'mse' (train_eco.py:148)")
+        if callable(loss):
+            raise NotImplementedError("a callable loss cannot run inside the TD kernel (eco_dqn_td_loss computes the "
+                                      "loss and its gradient on the device): pass 'mse' or 'huber'")
+        if not isinstance(loss, str) or loss not in ("mse", "huber"):
+            raise ValueError("loss must be 'huber', 'mse' or a callable")  # dqn.py:174
         if max_grad_norm is not None:
-            raise NotImplementedError("gradient clipping is not on the hot path (train_eco.py:138 uses None)")
+            if (isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, numbers.Real)
+                    or not math.isfinite(max_grad_norm) or max_grad_norm <= 0):
+                raise ValueError("max_grad_norm must be None or a finite positive number")
+            max_grad_norm = float(max_grad_norm)
+        self.loss = loss
+        self._loss_kind = _lib.ECO_LOSS_HUBER if loss == "huber" else _lib.ECO_LOSS_MSE
+        self.max_grad_norm = max_grad_norm
         self.env = envs
         self.graphs = envs.graphs
         self.device = envs.graphs.device
@@ -115,6 +126,9 @@ class DQN:
         self.grad = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.exp_avg = torch.zeros_like(self.grad)
         self.exp_avg_sq = torch.zeros_like(self.grad)
+        # max_grad_norm: {total_norm, clip coefficient} of the last train_step, written by eco_grad_clip
+        self.grad_norm = (torch.zeros(2, dtype=torch.float32, device=self.device) if max_grad_norm is not None
+                          else None)
         self.adam_step = 0
         self.grad_steps = 0
 
@@ -284,10 +298,18 @@ class DQN:
                                act=greedy, actions_out=self.a_star)
             scope_s = _lib.ECO_NORM_PER_CALL
         net.forward_graphs(xs, self.graphs, gid, norm_scope=scope_s, q_out=self.q_s, saved=self.saved)
-        _lib.check(_lib.lib.eco_dqn_td(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
-                                       _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
-                                       ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)), _lib.ptr(self.dq),
-                                       _lib.ptr(self.sqerr), _lib.ptr(loss_dev), _lib.stream_ptr()))
+        if self._loss_kind == _lib.ECO_LOSS_MSE:
+            _lib.check(_lib.lib.eco_dqn_td(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
+                                           _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
+                                           ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
+                                           _lib.ptr(self.dq), _lib.ptr(self.sqerr), _lib.ptr(loss_dev),
+                                           _lib.stream_ptr()))
+        else:  # loss="huber" (dqn.py:172): the same kernel's smooth-L1 instantiation
+            _lib.check(_lib.lib.eco_dqn_td_loss(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
+                                                _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
+                                                ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
+                                                self._loss_kind, _lib.ptr(self.dq), _lib.ptr(self.sqerr),
+                                                _lib.ptr(loss_dev), _lib.stream_ptr()))
         net.backward_graphs(xs, self.graphs, gid, self.saved, self.dq, self.grad, workspace=self.bw_ws)
         # RCCL sum over xGMI (233.7 KB) on the collective's stream, the mean folded into Adam; independent work
         # (the caller's `overlap`) is issued on this stream meanwhile
@@ -296,6 +318,11 @@ class DQN:
             overlap()
         if work is not None:
             work.wait()
+        if self.max_grad_norm is not None:
+            # clip_grad_norm_ (dqn.py:446-447) on the summed gradient: `scale` (1/world) enters the norm only, so the
+            # norm is the mean gradient's and Adam's own scale still applies to the clipped sum
+            _lib.check(_lib.lib.eco_grad_clip(_lib.ptr(self.grad), self.grad.numel(), scale, self.max_grad_norm,
+                                              _lib.ptr(self.grad_norm), _lib.stream_ptr()))
         self.adam_step += 1
         _lib.check(_lib.lib.eco_adam(_lib.ptr(net.flat), _lib.ptr(self.grad), _lib.ptr(self.exp_avg),
                                      _lib.ptr(self.exp_avg_sq), net.flat.numel(), self.lr, 0.9, 0.999,

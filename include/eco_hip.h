@@ -307,6 +307,34 @@ int eco_dqn_td(const float *q_s, const float *q_target_next, const int32_t *a_st
                const float *rewards, const float *dones, int32_t batch, int32_t n_spins, float gamma,
                int32_t clip_q_targets, float *dq, float *sqerr, float *loss, eco_stream_t stream);
 
+/* eco_dqn_td with the loss of DQN(loss=...) (dqn.py:172, applied at :440): the same arguments plus loss_kind.
+ * ECO_LOSS_MSE is F.mse_loss: exactly eco_dqn_td, bit for bit.  ECO_LOSS_HUBER is
+ * F.smooth_l1_loss(q_value, td_target, reduction='mean') with beta = 1: with d = q_s[b][a_b] - td, the per-sample
+ * loss is 0.5 d^2 for |d| < 1 and |d| - 0.5 otherwise; dq at a_b is d / B for |d| <= 1 and sign(d) / B beyond (zero
+ * elsewhere); sqerr[B] receives the per-sample losses and loss[1] their mean.  The TD target, clip_q_targets, the
+ * a_star gather and the index guards are those of eco_dqn_td (one kernel, two instantiations).  Any other
+ * loss_kind: ECO_ERR_ARG before any launch. */
+enum { ECO_LOSS_MSE = 0, ECO_LOSS_HUBER = 1 };
+int eco_dqn_td_loss(const float *q_s, const float *q_target_next, const int32_t *a_star, const int32_t *actions,
+                    const float *rewards, const float *dones, int32_t batch, int32_t n_spins, float gamma,
+                    int32_t clip_q_targets, int32_t loss_kind, float *dq, float *sqerr, float *loss,
+                    eco_stream_t stream);
+
+/* torch.nn.utils.clip_grad_norm_(network.parameters(), max_norm), norm type 2 (dqn.py:446-447), on the flat
+ * gradient, between the gradient all-reduce and eco_adam:
+ *   total_norm = grad_scale * sqrt(sum_i grad[i]^2),  coef = min(1, max_norm / (total_norm + 1e-6)),
+ *   grad[i] *= coef in place (as torch leaves p.grad),  norm_out[2] (device) = {total_norm, coef}.
+ * grad_scale is the 1/world that eco_adam applies later: it enters the norm only, and the in-place factor is coef
+ * alone, so eco_adam's own grad_scale still yields coef * grad / world.  The sum of squares is accumulated in
+ * float64 (a single 1e30 element does not overflow it) in a fixed order -- per-workgroup partial sums in a
+ * library-owned device buffer, then one workgroup over the partials; grids sized from n -- with no atomics and no
+ * host read: bitwise reproducible run to run.  total_norm and coef are formed in float64 and rounded to fp32 once
+ * each.  coef == 1 leaves grad untouched (a zero gradient included).  A non-finite gradient propagates as torch's
+ * error_if_nonfinite=False does: an infinite norm gives coef 0 (finite elements become 0, infinite ones NaN), a
+ * NaN norm gives coef NaN and every element NaN.  Calls on different streams of one device share the partial
+ * buffer and must not overlap.  max_norm <= 0 or non-finite, n <= 0, null pointers: ECO_ERR_ARG before any launch. */
+int eco_grad_clip(float *grad, int32_t n, double grad_scale, double max_norm, float *norm_out, eco_stream_t stream);
+
 /* torch.optim.Adam step (dqn.py:212, optimizer.step() :449) on a flat fp32 buffer.
  * grad_scale multiplies the gradient first (1/world after a multi-GPU sum all-reduce). */
 int eco_adam(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, int32_t n, double lr,
