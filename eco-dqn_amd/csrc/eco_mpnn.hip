@@ -877,8 +877,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
 // exact-f32 MFMA tiles as the LDS kernels with both layer weights staged in LDS (8 waves: the gathers
 // and the 8-chunk Linears need more than the 128 VGPRs of a 16-wave workgroup).
 // LDS: Wl [2][64][LDW] | readout scratch
-template <int NW, bool FW = false>
+// XW: floats per observation row, 8 or 16 (n_obs_in > 8, MAIN_OBSERVABLES).  The wide instance adds features
+// 8..15 to the two 8-input Linears from PK_WXH / PK_W0H in the summation order of mpnn_forward_kernel's xdot_hi:
+// the low eight products, then the high eight as one term.
+template <int NW, bool FW = false, int XW = 8>
 __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs a, float* hbuf) {
+  static_assert(XW == 8 || XW == 16, "observation rows are 8 or 16 floats");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   ws_invalidate_key(a.call_maxdeg);  // hbuf overwrites the cached shared-graph tables
   const int lane = threadIdx.x & 63;
@@ -902,20 +906,32 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
   const int gid = a.gids[e];
   const uint32_t* __restrict__ eg = a.gs.edges + a.gs.edge_base[gid];
   const double* __restrict__ ewg = a.gs.edge_weights + a.gs.edge_base[gid];  // FW only
-  const float* x = a.x + R0 * 8;
+  const float* x = a.x + R0 * XW;
   auto rinfo = [&](int r) { return row_info_packed(pack_row_info(a, e, r, N)); };
+  // w . x over features 8..15 of row r (wide rows)
+  auto xdot_hi = [&](int r, const float (&wh)[8]) {
+    const float4 x2 = f4(x + r * XW + 8), x3 = f4(x + r * XW + 12);
+    return wh[0] * x2.x + wh[1] * x2.y + wh[2] * x2.z + wh[3] * x2.w + wh[4] * x3.x + wh[5] * x3.y + wh[6] * x3.z +
+           wh[7] * x3.w;
+  };
 
   // ---- phase A: Z = Wx . x into HB ----
   {
     float wx[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) wx[k] = P[PK_WX + lane * 8 + k];
+    float wxh[8];
+    if constexpr (XW == 16) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) wxh[k] = P[PK_WXH + lane * 8 + k];
+    }
     for (int r = w; r < rows_pad; r += NW) {
       float z = 0.f;
       if (r < N) {
-        const float4 x0 = f4(x + r * 8), x1 = f4(x + r * 8 + 4);
+        const float4 x0 = f4(x + r * XW), x1 = f4(x + r * XW + 4);
         z = wx[0] * x0.x + wx[1] * x0.y + wx[2] * x0.z + wx[3] * x0.w + wx[4] * x1.x + wx[5] * x1.y +
             wx[6] * x1.z + wx[7] * x1.w;
+        if constexpr (XW == 16) z = z + xdot_hi(r, wxh);
       }
       HB[(size_t)r * 64 + lane] = z;
     }
@@ -969,12 +985,21 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
     float w0[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) w0[k] = P[PK_W0 + lane * 8 + k];
+    float w0h[8];
+    if constexpr (XW == 16) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w0h[k] = P[PK_W0H + lane * 8 + k];
+    }
     for (int r = w; r < rows_pad; r += NW) {
       float h0 = 0.f;
       if (r < N) {
-        const float4 x0 = f4(x + r * 8), x1 = f4(x + r * 8 + 4);
-        h0 = relu(w0[0] * x0.x + w0[1] * x0.y + w0[2] * x0.z + w0[3] * x0.w + w0[4] * x1.x + w0[5] * x1.y +
-                  w0[6] * x1.z + w0[7] * x1.w);
+        const float4 x0 = f4(x + r * XW), x1 = f4(x + r * XW + 4);
+        if constexpr (XW == 16)
+          h0 = relu(w0[0] * x0.x + w0[1] * x0.y + w0[2] * x0.z + w0[3] * x0.w + w0[4] * x1.x + w0[5] * x1.y +
+                    w0[6] * x1.z + w0[7] * x1.w + xdot_hi(r, w0h));
+        else
+          h0 = relu(w0[0] * x0.x + w0[1] * x0.y + w0[2] * x0.z + w0[3] * x0.w + w0[4] * x1.x + w0[5] * x1.y +
+                    w0[6] * x1.z + w0[7] * x1.w);
       }
       HA[(size_t)r * 64 + lane] = h0;
     }
@@ -1073,8 +1098,6 @@ static int prepare(MpnnArgs& a, const float* packed, int32_t n_obs_in, const eco
   a = MpnnArgs{};
   a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = N; a.gpb = graphs_per_block(N, batch);
   a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
-  if (a.xw != 8 && N > MPNN_MAX_SPINS)
-    return fail(ECO_ERR_ARG, "more than 8 node features need N <= 512 (the N > 512 kernel takes 8-float rows)");
   a.err = err_word();
   return ECO_OK;
 }
@@ -1267,15 +1290,21 @@ extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco
       return mpnn_forward_shared_launch(a, workspace, st);
     const int rows_pad = (N + 15) & ~15;
     const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
+#define ECO_LAUNCH_LARGE(FW, XW)                                                                       \
+  do {                                                                                                \
+    (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8, FW, XW>,                      \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
+    mpnn_forward_large_kernel<8, FW, XW><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256)); \
+  } while (0)
+    const bool wide = a.xw == 16;  // more than 8 observables: 16-float rows
     if (gs->edge_weights) {
-      (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      mpnn_forward_large_kernel<8, true><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256));
-      return check_launch("mpnn_forward_large");
+      if (wide) ECO_LAUNCH_LARGE(true, 16);
+      else ECO_LAUNCH_LARGE(true, 8);
+    } else {
+      if (wide) ECO_LAUNCH_LARGE(false, 16);
+      else ECO_LAUNCH_LARGE(false, 8);
     }
-    (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    mpnn_forward_large_kernel<8><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256));
+#undef ECO_LAUNCH_LARGE
     return check_launch("mpnn_forward_large");
   }
   const int blocks = (batch + a.gpb - 1) / a.gpb;

@@ -50,6 +50,14 @@ constexpr int AG_NW = AG_NW_X;         // waves per aggregation workgroup (8: 25
 #define AG_TPW_X 2
 #endif
 constexpr int AG_TPW = AG_TPW_X;       // aggregation tile pairs per wave in flight together
+#ifndef AG_NW16_X
+#define AG_NW16_X 8
+#endif
+#ifndef AG_TPW16_X
+#define AG_TPW16_X 2
+#endif
+constexpr int AG_NW16 = AG_NW16_X;     // the same two for the x-build instances on 16-float observation rows: their
+constexpr int AG_TPW16 = AG_TPW16_X;   // x values (32 per lane at 16 waves) do not fit 128 VGPRs beside the pair tables
 constexpr int AG_UNROLL = 4;           // a tile's rows are padded to multiples of 4 edges (one 8-B word group)
 
 struct SharedBufs {
@@ -261,6 +269,23 @@ __device__ __forceinline__ f32x4 lin8_chunk(const float* W, int c, float xk0, fl
   return __builtin_amdgcn_mfma_f32_16x16x4f32(wl[c * 128 + 4], xk1, d, 0, 0, 0);
 }
 
+// The 16-input form of lin8 (observation rows of 16 floats, n_obs_in > 8): the two K-steps of lin8 on W [64][8]
+// (features 0..7), then two more on WH [64][8] (features 8..15: PK_W0H / PK_WXH) with xk2 = x[8 + (l >> 4)] and
+// xk3 = x[12 + (l >> 4)].  shared_agg_kernel's wide x-build runs the same four MFMAs in the same order on its LDS
+// copy of the weights, so the h0 rebuilt by the first update layer equals the h0 the aggregation summed.
+__device__ __forceinline__ void lin16(f32x4 (&d)[4], const float* W, const float* WH, float xk0, float xk1, float xk2,
+                                      float xk3, int lane) {
+  const float* wl = W + (lane & 15) * 8 + (lane >> 4);
+  const float* wh = WH + (lane & 15) * 8 + (lane >> 4);
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt) {
+    d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[nt * 128], xk0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[nt * 128 + 4], xk1, d[nt], 0, 0, 0);
+    d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wh[nt * 128], xk2, d[nt], 0, 0, 0);
+    d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wh[nt * 128 + 4], xk3, d[nt], 0, 0, 0);
+  }
+}
+
 // aggregation tile tables: tile t, slot k -> node perm[16 t + k]; the tile's CSR rows interleaved (padding words
 // 0: column 0, weight 0) in a BANK-AWARE order, and the tile's longest row (slot 0: ranked first).
 // In shared_agg_kernel lane 2k + q reads 16 B of the 32-B row col of slot k's current edge (a wave: slots 0..15
@@ -413,25 +438,34 @@ __global__ __launch_bounds__(SP_THREADS) void shared_pack_kernel(SharedBufs sb) 
 // XSRC 0: the block is read from src; 1 / 2 / 3: it is BUILT from the observation rows x (32 B per node) as
 // U = relu(Wx.x + w_a) / V = relu(Wx.x - w_a) / h0 = relu(W0.x) (mpnn.py:89-104, :55) with lin8_chunk: the
 // next item's x values are what is prefetched, the Linear runs when the block is written to LDS.
+// XW: floats per observation row (XSRC 1..3).  16 (n_obs_in > 8): two more x values per tile are prefetched and the
+// build runs four K-steps (lin16's order), its weight block AG_WL16 floats; the 8-wide instances are unchanged.
 constexpr int AG_LDS = 160 * 1024;                               // dynamic LDS of the aggregation launches
 constexpr int AG_WL = 576;                                        // floats of the x-build weights (64 x 8 + 64)
+// 16-float observation rows (XW = 16): the weights of features 8..15 (64 x 8: PK_W0H / PK_WXH) follow the AG_WL block
+constexpr int AG_WL16 = AG_WL + 512;
 constexpr int AG_PF = (4096 + 64 * AG_NW - 1) / (64 * AG_NW);  // float4 per thread per block: 64 KB (N <= 2048)
 constexpr int AG_XT = (2048 / 16 + AG_NW - 1) / AG_NW;          // 16-node x tiles per wave (N <= 2048)
 // A wave's tile pairs are the same for every item: p = w + (r AG_TPW + j) AG_NW, rounds r < AG_R.  Their row
 // lengths, table offsets and output nodes are read once per workgroup into registers (global loads inside the item
 // loop would wait for the next block's prefetch too: vmcnt counts in order).
-constexpr int AG_R = (2048 / 32 + AG_TPW * AG_NW - 1) / (AG_TPW * AG_NW);
+// TPW, NW: tile pairs in flight per wave and waves per workgroup of the instance (AG_TPW, AG_NW; the x-build on
+// 16-float rows: AG_TPW16, AG_NW16)
+template <int TPW, int NW>
 struct AgPairs {
-  int base[AG_R][AG_TPW], ml[AG_R][AG_TPW], mlw[AG_R][AG_TPW], nd[AG_R][AG_TPW];
+  static constexpr int R = (2048 / 32 + TPW * NW - 1) / (TPW * NW);
+  int base[R][TPW], ml[R][TPW], mlw[R][TPW], nd[R][TPW];
 };
-__device__ __forceinline__ void sh_agg_pairs(const SharedBufs& sb, AgPairs& P, int w, int lane) {
+template <int TPW, int NW>
+__device__ __forceinline__ void sh_agg_pairs(const SharedBufs& sb, AgPairs<TPW, NW>& P, int w, int lane) {
+  constexpr int AG_R = AgPairs<TPW, NW>::R;
   const int k = lane >> 1;
   const int jt = k >> 4, slot = k & 15;
 #pragma unroll
   for (int r = 0; r < AG_R; ++r)
 #pragma unroll
-    for (int j = 0; j < AG_TPW; ++j) {
-      const int p = w + (r * AG_TPW + j) * AG_NW;
+    for (int j = 0; j < TPW; ++j) {
+      const int p = w + (r * TPW + j) * NW;
       const int t = 2 * p + jt;
       const bool live = 2 * p < sb.nt16 && t < sb.nt16;
       P.ml[r][j] = live ? sb.tml[t] : 0;
@@ -442,9 +476,10 @@ __device__ __forceinline__ void sh_agg_pairs(const SharedBufs& sb, AgPairs& P, i
 }
 // one item: every node's sums over its row of the packed table, the block in LDS (HL); MODE 0: weights +-1,
 // +1: the +1 edges with weight 1, -1: the -1 edges with weight 1
-template <bool LDSW, int MODE, bool UNIT, int RB>
-__device__ __forceinline__ void sh_agg_item(const AgPairs& P, int nt16, const float4* HL, const uint16_t* tab,
+template <bool LDSW, int MODE, bool UNIT, int RB, int TPW, int NW>
+__device__ __forceinline__ void sh_agg_item(const AgPairs<TPW, NW>& P, int nt16, const float4* HL, const uint16_t* tab,
                                             int zoff, float* dst, int accumulate, int w, int lane) {
+  constexpr int AG_R = AgPairs<TPW, NW>::R;
   const int q = lane & 1;
   typedef uint16_t __attribute__((ext_vector_type(4))) u16x4;
   typedef float f2v __attribute__((ext_vector_type(2)));
@@ -452,28 +487,28 @@ __device__ __forceinline__ void sh_agg_item(const AgPairs& P, int nt16, const fl
   const uint32_t qoff = 16u * (uint32_t)q;
 #pragma unroll
   for (int r = 0; r < AG_R; ++r) {
-    if (2 * (w + r * AG_TPW * AG_NW) >= nt16) break;  // wave-uniform
-    u16x4 cur[AG_TPW], nxt[AG_TPW] = {};
-    f2v a01[AG_TPW], a23[AG_TPW];  // the lane's four sums as two packed pairs (v_pk_fma_f32)
+    if (2 * (w + r * TPW * NW) >= nt16) break;  // wave-uniform
+    u16x4 cur[TPW], nxt[TPW] = {};
+    f2v a01[TPW], a23[TPW];  // the lane's four sums as two packed pairs (v_pk_fma_f32)
     // reads are never predicated: a lane past its row reads the zero words at zoff (a conditional select of the
     // loaded value would make the compiler wait for it at once)
 #pragma unroll
-    for (int j = 0; j < AG_TPW; ++j) {
+    for (int j = 0; j < TPW; ++j) {
       a01[j] = a23[j] = f2v{0.f, 0.f};
       cur[j] = *reinterpret_cast<const u16x4*>(tab + (P.ml[r][j] > 0 ? P.base[r][j] : zoff));
     }
     for (int i = 0; i < P.mlw[r][0]; i += 4) {
 #pragma unroll
-      for (int j = 0; j < AG_TPW; ++j)
+      for (int j = 0; j < TPW; ++j)
         if (i + 4 < P.mlw[r][j])  // wave-uniform
           nxt[j] = *reinterpret_cast<const u16x4*>(tab + (i + 4 < P.ml[r][j] ? P.base[r][j] + (i + 4) * 16 : zoff));
       // this step's row reads first (RB edges of each pair at a time), then the sums
 #pragma unroll
       for (int u0 = 0; u0 < 4; u0 += RB) {
-        float4 h[AG_TPW][RB];
-        float f[AG_TPW][RB];
+        float4 h[TPW][RB];
+        float f[TPW][RB];
 #pragma unroll
-        for (int j = 0; j < AG_TPW; ++j) {
+        for (int j = 0; j < TPW; ++j) {
           if (i < P.mlw[r][j]) {  // wave-uniform
             const uint2 wd = __builtin_bit_cast(uint2, cur[j]);
 #pragma unroll
@@ -489,7 +524,7 @@ __device__ __forceinline__ void sh_agg_item(const AgPairs& P, int nt16, const fl
           }
         }
 #pragma unroll
-        for (int j = 0; j < AG_TPW; ++j) {
+        for (int j = 0; j < TPW; ++j) {
           if (i < P.mlw[r][j]) {
 #pragma unroll
             for (int v = 0; v < RB; ++v) {
@@ -505,14 +540,14 @@ __device__ __forceinline__ void sh_agg_item(const AgPairs& P, int nt16, const fl
         }
       }
 #pragma unroll
-      for (int j = 0; j < AG_TPW; ++j) {
+      for (int j = 0; j < TPW; ++j) {
         if (i < P.mlw[r][j]) {
           cur[j] = nxt[j];
         }
       }
     }
 #pragma unroll
-    for (int j = 0; j < AG_TPW; ++j) {
+    for (int j = 0; j < TPW; ++j) {
       if (P.nd[r][j] >= 0) {
         float* d = dst + (size_t)P.nd[r][j] * SH_FC + 4 * q;
         float4 o = make_float4(a01[j].x, a01[j].y, a23[j].x, a23[j].y);
@@ -525,22 +560,26 @@ __device__ __forceinline__ void sh_agg_item(const AgPairs& P, int nt16, const fl
     }
   }
 }
-template <int XSRC>
-__global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, SharedBufs sb, const float* src,
+template <int XSRC, int XW = 8, int NW = (XW == 16 ? AG_NW16 : AG_NW)>
+__global__ __launch_bounds__(64 * NW, 1) void shared_agg_kernel(MpnnArgs a, SharedBufs sb, const float* src,
                                                                    int mode, int accumulate, int items) {
+  static_assert(XW == 8 || (XW == 16 && XSRC != 0), "observation rows are 8 or 16 floats");
+  constexpr int WL = XW == 16 ? AG_WL16 : AG_WL;
   // mode (the host's +1 / -1 / 0 per launch) must match XSRC: 1 -> +1, 2 -> -1, 0 / 3 -> 0
   extern __shared__ __attribute__((aligned(16))) float4 HL[];  // [N][2], then the packed edge table
   const int N = a.N;
   if (mode < 0 && !(a.gs.meta[(size_t)a.gids[0] * 4 + 2] < 0.0)) return;  // no -1 edge: A- . V = 0
   const int n2 = N * 2;
+  static_assert(XSRC != 0 || NW == AG_NW, "AG_PF is sized for AG_NW waves");
   constexpr int NPF = XSRC ? 1 : AG_PF;
-  constexpr int NXT = XSRC ? AG_XT : 1;
+  constexpr int NXT = XSRC ? (2048 / 16 + NW - 1) / NW : 1;  // 16-node x tiles per wave (AG_XT at AG_NW waves)
   float4 pf[NPF];
   float xk0[NXT], xk1[NXT];
+  float xk2[XW == 16 ? NXT : 1], xk3[XW == 16 ? NXT : 1];  // features 8..15 (wide rows)
   int pc = 0;  // chunk of the prefetched item (XSRC)
   // XSRC: the 8-input Linear (W0 or Wx: 64 x 8) and w_a sit at the end of the LDS (AG_WL floats), read per item
   // (global reads inside the build would expose an L2 round trip per item; registers would spill)
-  float* WLs = reinterpret_cast<float*>(reinterpret_cast<char*>(HL) + AG_LDS) - AG_WL;
+  float* WLs = reinterpret_cast<float*>(reinterpret_cast<char*>(HL) + AG_LDS) - WL;
   const int wv_ = threadIdx.x >> 6, ln = threadIdx.x & 63;
   // the k-th item of this workgroup (-1: none).  XSRC 0: items blockIdx.x + k grid.  XSRC 1..3: the workgroup
   // walks whole episodes, their 8 chunks in a row (episode blockIdx.x + (k / 8) grid, chunk k % 8), so an episode's
@@ -559,7 +598,7 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
       const float* S = src + (size_t)it * N * SH_FC;
 #pragma unroll
       for (int u = 0; u < NPF; ++u) {
-        const int i = threadIdx.x + u * 64 * AG_NW;
+        const int i = threadIdx.x + u * 64 * NW;
         pf[u] = f4_nt(S + 4 * (size_t)min(i, n2 - 1));
       }
     } else {
@@ -571,10 +610,14 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
       for (int j = 0; j < NXT; ++j) {
         // unpredicated loads (a predicated load compiles to a branch and a wait per load): a padding episode
         // reads episode B - 1's rows and reaches only its own rows; nodes past N are not stored
-        const int n = min((wv_ + j * AG_NW) * 16 + (ln & 15), N - 1);
-        const float* xr = a.x + ((size_t)min(ep, a.B - 1) * N + n) * 8 + (ln >> 4);
+        const int n = min((wv_ + j * NW) * 16 + (ln & 15), N - 1);
+        const float* xr = a.x + ((size_t)min(ep, a.B - 1) * N + n) * XW + (ln >> 4);
         xk0[j] = xr[0];
         xk1[j] = xr[4];
+        if constexpr (XW == 16) {
+          xk2[j] = xr[8];
+          xk3[j] = xr[12];
+        }
       }
     }
   };
@@ -582,7 +625,7 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
     if (XSRC == 0) {
 #pragma unroll
       for (int u = 0; u < NPF; ++u) {
-        const int i = threadIdx.x + u * 64 * AG_NW;
+        const int i = threadIdx.x + u * 64 * NW;
         if (i < n2) HL[i] = pf[u];
       }
     } else {
@@ -590,15 +633,24 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
       const bool mine = (ln >> 5) == (pc & 1);
       const float* wl = WLs + (ln & 15) * 8 + (ln >> 4) + (pc >> 1) * 128;
       const float wv0 = wl[0], wv1 = wl[4];
+      float wv2 = 0.f, wv3 = 0.f;
+      if constexpr (XW == 16) {
+        wv2 = wl[AG_WL];
+        wv3 = wl[AG_WL + 4];
+      }
       const float4 wa = XSRC == 3 ? make_float4(0.f, 0.f, 0.f, 0.f)
                                   : *reinterpret_cast<const float4*>(WLs + 512 + 16 * (pc >> 1) + 4 * (ln >> 4));
 #pragma unroll
       for (int j = 0; j < NXT; ++j) {
-        const int n = (wv_ + j * AG_NW) * 16 + (ln & 15);
-        if ((wv_ + j * AG_NW) * 16 >= N) break;  // wave-uniform: MFMAs below run with EXEC all ones
+        const int n = (wv_ + j * NW) * 16 + (ln & 15);
+        if ((wv_ + j * NW) * 16 >= N) break;  // wave-uniform: MFMAs below run with EXEC all ones
         // lin8_chunk on the preloaded weights (the same two MFMAs)
         f32x4 z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv0, xk0[j], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv1, xk1[j], z, 0, 0, 0);
+        if constexpr (XW == 16) {  // features 8..15: lin16's third and fourth K-step
+          z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv2, xk2[j], z, 0, 0, 0);
+          z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv3, xk3[j], z, 0, 0, 0);
+        }
         const float sg = XSRC == 2 ? -1.f : 1.f;
         float4 v = XSRC == 3 ? relu4(z)
                              : make_float4(relu(fmaf(sg, wa.x, z[0])), relu(fmaf(sg, wa.y, z[1])),
@@ -611,10 +663,12 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
   if (item < 0) return;
   const int nwords = sb.toff[sb.nt16];
   // LDS: the block's N rows, the zero row N, the packed table ... the x-build weights at the end
-  const bool in_lds = (size_t)(n2 + 2) * 16 + (size_t)(nwords + AG_ZW) * 2 + AG_WL * 4 <= (size_t)AG_LDS;  // uniform
+  const bool in_lds = (size_t)(n2 + 2) * 16 + (size_t)(nwords + AG_ZW) * 2 + WL * 4 <= (size_t)AG_LDS;  // uniform
   if (XSRC)
-    for (int i = threadIdx.x; i < AG_WL; i += 64 * AG_NW)
+    for (int i = threadIdx.x; i < AG_WL; i += 64 * NW)
       WLs[i] = i < 512 ? a.P[(XSRC == 3 ? PK_W0 : PK_WX) + i] : (i < 576 ? a.P[PK_WA + i - 512] : 0.f);
+  if constexpr (XW == 16)
+    for (int i = threadIdx.x; i < 512; i += 64 * NW) WLs[AG_WL + i] = a.P[(XSRC == 3 ? PK_W0H : PK_WXH) + i];
   uint16_t* T16 = reinterpret_cast<uint16_t*>(HL + n2 + 2);                           // 16-B aligned
   // no -1 edge and N < 2048 (padding on the zero row): every word is a +1 edge (A+ = A; the A- pass returned above)
   const bool unit = N < 2048 && !(a.gs.meta[(size_t)a.gids[0] * 4 + 2] < 0.0);
@@ -622,11 +676,13 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
   if (in_lds) {
     const uint4* s4p = reinterpret_cast<const uint4*>(sb.et16);
     uint4* d4p = reinterpret_cast<uint4*>(T16);
-    for (int i = threadIdx.x; i < (nwords + AG_ZW) / 8; i += 64 * AG_NW) d4p[i] = s4p[i];  // multiples of 64
+    for (int i = threadIdx.x; i < (nwords + AG_ZW) / 8; i += 64 * NW) d4p[i] = s4p[i];  // multiples of 64
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  AgPairs P;
-  sh_agg_pairs(sb, P, w, lane);
+  // wide rows: AG_NW16 waves (twice the registers per lane for twice the x values), AG_TPW16 pairs in flight
+  constexpr int TPW = XW == 16 ? AG_TPW16 : AG_TPW;
+  AgPairs<TPW, NW> P;
+  sh_agg_pairs<TPW, NW>(sb, P, w, lane);
   if (XSRC) __syncthreads();  // the x-build weights
   load_block(item, 0);
   store_block();
@@ -639,9 +695,9 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
     float* dst = sb.AG + (size_t)item * N * SH_FC;
     // row reads in flight per pair: 4 edges (2: measured slower where the x prefetch holds registers)
     constexpr int RB = 4;
-    if (in_lds && unit) sh_agg_item<true, MODE, true, RB>(P, sb.nt16, HL, T16, nwords, dst, accumulate, w, lane);
-    else if (in_lds) sh_agg_item<true, MODE, false, RB>(P, sb.nt16, HL, T16, nwords, dst, accumulate, w, lane);
-    else sh_agg_item<false, MODE, false, RB>(P, sb.nt16, HL, sb.et16, nwords, dst, accumulate, w, lane);
+    if (in_lds && unit) sh_agg_item<true, MODE, true, RB, TPW, NW>(P, sb.nt16, HL, T16, nwords, dst, accumulate, w, lane);
+    else if (in_lds) sh_agg_item<true, MODE, false, RB, TPW, NW>(P, sb.nt16, HL, T16, nwords, dst, accumulate, w, lane);
+    else sh_agg_item<false, MODE, false, RB, TPW, NW>(P, sb.nt16, HL, sb.et16, nwords, dst, accumulate, w, lane);
     __syncthreads();  // every wave is done with this block
     if (more) store_block();
     __syncthreads();
@@ -653,7 +709,8 @@ __global__ __launch_bounds__(64 * AG_NW, 1) void shared_agg_kernel(MpnnArgs a, S
 // Persistent workgroups (weights LDS-DMA-staged once); wave items = Linear tiles (slice-major, node tiles of
 // SH_NPT consecutive nodes), lane row c16 = node kn x episode eps.  Rows of padding episodes and nodes are
 // computed but stored as zeros / not stored.
-template <int PHASE>
+// XW: floats per observation row (only layer 0 of PHASE 1, Hc == nullptr, reads x): 16 rebuilds h0 with lin16.
+template <int PHASE, int XW = 8>
 __global__ __launch_bounds__(64 * SH_NW, 1) void shared_lin_kernel(MpnnArgs a, SharedBufs sb, int layer,
                                                                    const float* Hc, float* Hn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -678,6 +735,7 @@ __global__ __launch_bounds__(64 * SH_NW, 1) void shared_lin_kernel(MpnnArgs a, S
   struct Rows {
     float4 ag[4], ev[4], hc[4];
     float xk0, xk1;
+    float xh[XW == 16 ? 2 : 0];  // x[8 + s4], x[12 + s4] (wide rows)
   };
   auto load_rows = [&](Rows& R, int it) {
     const int s = it / sb.ntiles, t = it - s * sb.ntiles;
@@ -690,14 +748,18 @@ __global__ __launch_bounds__(64 * SH_NW, 1) void shared_lin_kernel(MpnnArgs a, S
     if (PHASE != 0) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) R.ev[c] = f4_nt(sb.EB + ro + c * cs);
-      if (Hc) {
+      if (XW == 8 && Hc) {  // the wide instance is layer 0 only: it always rebuilds h0
 #pragma unroll
         for (int c = 0; c < 4; ++c) R.hc[c] = f4_nt(Hc + ro + c * cs);
       } else {
         // unpredicated (clamped) loads: rows of padding episodes and nodes are stored as zeros
-        const float* xr = a.x + ((size_t)min(ep, a.B - 1) * N + nc) * 8 + s4;
+        const float* xr = a.x + ((size_t)min(ep, a.B - 1) * N + nc) * XW + s4;
         R.xk0 = xr[0];
         R.xk1 = xr[4];
+        if constexpr (XW == 16) {
+          R.xh[0] = xr[8];
+          R.xh[1] = xr[12];
+        }
       }
     }
   };
@@ -758,12 +820,13 @@ __global__ __launch_bounds__(64 * SH_NW, 1) void shared_lin_kernel(MpnnArgs a, S
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) hn[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
       float4 hc[4];
-      if (Hc) {
+      if (XW == 8 && Hc) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) hc[c] = cu.hc[c];
       } else {  // layer 0: h0 = relu(W0 . x) of this lane's row (lin8, as the aggregation built it)
         f32x4 z[4];
-        lin8(z, P + PK_W0, cu.xk0, cu.xk1, lane);
+        if constexpr (XW == 16) lin16(z, P + PK_W0, P + PK_W0H, cu.xk0, cu.xk1, cu.xh[0], cu.xh[1], lane);
+        else lin8(z, P + PK_W0, cu.xk0, cu.xk1, lane);
 #pragma unroll
         for (int c = 0; c < 4; ++c) hc[c] = relu4(z[c]);
       }
@@ -916,6 +979,14 @@ static int mpnn_forward_shared_launch(const MpnnArgs& a, void* workspace, hipStr
   (void)hipFuncSetAttribute((const void*)shared_agg_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
   (void)hipFuncSetAttribute((const void*)shared_agg_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
   (void)hipFuncSetAttribute((const void*)shared_agg_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
+  const bool wide = a.xw == 16;  // more than 8 observables: the x-build instances for 16-float rows
+  if (wide) {
+    (void)hipFuncSetAttribute((const void*)shared_agg_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
+    (void)hipFuncSetAttribute((const void*)shared_agg_kernel<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
+    (void)hipFuncSetAttribute((const void*)shared_agg_kernel<3, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_agg);
+    (void)hipFuncSetAttribute((const void*)shared_lin_kernel<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(64 * FH_FRAG * 2));
+  }
   const int grid = shared_grid();
   const size_t lds_edge = 16 * FH_FRAG * 2, lds_layer = 64 * FH_FRAG * 2;
   (void)hipFuncSetAttribute((const void*)shared_lin_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -925,11 +996,21 @@ static int mpnn_forward_shared_launch(const MpnnArgs& a, void* workspace, hipStr
   (void)hipFuncSetAttribute((const void*)shared_lin_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_layer);
   // edge phase: A+ . U (+ A- . V; that pass returns at once on graphs without -1 edges, meta[2] on the device)
-  shared_agg_kernel<1><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, 1, 0, items);
-  shared_agg_kernel<2><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, -1, 1, items);
+  if (wide) {
+    shared_agg_kernel<1, 16><<<agrid, 64 * AG_NW16, lds_agg, st>>>(a, sb, nullptr, 1, 0, items);
+    shared_agg_kernel<2, 16><<<agrid, 64 * AG_NW16, lds_agg, st>>>(a, sb, nullptr, -1, 1, items);
+  } else {
+    shared_agg_kernel<1><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, 1, 0, items);
+    shared_agg_kernel<2><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, -1, 1, items);
+  }
   shared_lin_kernel<0><<<grid, 64 * SH_NW, lds_edge, st>>>(a, sb, 0, nullptr, nullptr);
-  shared_agg_kernel<3><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, 0, 0, items);       // A . h0
-  shared_lin_kernel<1><<<grid, 64 * SH_NW, lds_layer, st>>>(a, sb, 0, nullptr, sb.HB);           // h1
+  if (wide) {
+    shared_agg_kernel<3, 16><<<agrid, 64 * AG_NW16, lds_agg, st>>>(a, sb, nullptr, 0, 0, items);   // A . h0
+    shared_lin_kernel<1, 16><<<grid, 64 * SH_NW, lds_layer, st>>>(a, sb, 0, nullptr, sb.HB);     // h1
+  } else {
+    shared_agg_kernel<3><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, nullptr, 0, 0, items);       // A . h0
+    shared_lin_kernel<1><<<grid, 64 * SH_NW, lds_layer, st>>>(a, sb, 0, nullptr, sb.HB);         // h1
+  }
   shared_agg_kernel<0><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, sb.HB, 0, 0, items);
   shared_lin_kernel<1><<<grid, 64 * SH_NW, lds_layer, st>>>(a, sb, 1, sb.HB, sb.HA);             // h2
   shared_agg_kernel<0><<<agrid, 64 * AG_NW, lds_agg, st>>>(a, sb, sb.HA, 0, 0, items);
