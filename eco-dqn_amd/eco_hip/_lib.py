@@ -57,6 +57,14 @@ class GraphSet(ctypes.Structure):
                 ("edge_weights", ctypes.c_void_p)]
 
 
+class EnvHistory(ctypes.Structure):
+    """eco_env_history: caller-owned device buffers of `rows` history rows; a NULL pointer is not recorded."""
+    _fields_ = [("rows", ctypes.c_int32), ("action", ctypes.c_void_p), ("solution", ctypes.c_void_p),
+                ("reward", ctypes.c_void_p), ("qs", ctypes.c_void_p), ("spins", ctypes.c_void_p),
+                ("score_mask", ctypes.c_void_p), ("valid", ctypes.c_void_p), ("length", ctypes.c_void_p),
+                ("score", ctypes.c_void_p)]
+
+
 class Replay(ctypes.Structure):
     _fields_ = [("capacity", ctypes.c_int32), ("n_spins", ctypes.c_int32), ("x_stride", ctypes.c_int32),
                 ("xs", ctypes.c_void_p),
@@ -83,6 +91,8 @@ _SIG = {
     "eco_env_step": (ctypes.c_int, [ctypes.POINTER(EnvConfig), ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P,
                                     _P, _P]),
     "eco_env_read": (ctypes.c_int, [ctypes.POINTER(EnvConfig), _P, _I, _P, _P, _P, _P]),
+    "eco_env_record": (ctypes.c_int, [ctypes.POINTER(EnvConfig), ctypes.POINTER(GraphSet), _P, _I, _I, _P, _P, _P,
+                                      _P, ctypes.POINTER(EnvHistory), _P]),
     "eco_check_errors": (ctypes.c_int, [_P]),
     "eco_error_word_copy": (ctypes.c_int, [_P, _P]),
     "eco_set_kernel_paths": (_I, [_I]),

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from .envs.batched import VecSpinSystem
+from .envs.history import History
 from .envs.utils import SpinBasis
 from .graphs import GraphStore
 
@@ -102,17 +103,30 @@ def _greedy(env):
     return st["best_solution"].cpu().numpy(), st["best_spins"].cpu().numpy().astype(np.float64)
 
 
+def _history_columns(hist):
+    """A rollout History -> the per-attempt lists of experiments/utils.py:276-279 (the `.T.tolist()` of the
+    per-step rows): actions [None, a_1, ...] (ints), scores [s_0, s_1, ...], rewards [None, r_1, ...]."""
+    ln = hist.length.cpu().numpy()
+    a, sc, r = hist.action.cpu().numpy(), hist.score.cpu().numpy(), hist.reward.cpu().numpy()
+    acts = [[None] + [int(x) for x in a[1:ln[e], e]] for e in range(len(ln))]
+    scores = [[float(x) for x in sc[:ln[e], e]] for e in range(len(ln))]
+    rews = [[None] + [float(x) for x in r[1:ln[e], e]] for e in range(len(ln))]
+    return acts, scores, rews, ln
+
+
 def test_network(network, env_args, graphs_test, device=None, step_factor=1, batched=True, n_attempts=50,
                  return_raw=False, return_history=False, max_batch_size=None, seed=None):
     """experiments/utils.py:22-31.  `network`: eco_hip MPNN.  Attempts are batched on the GPU
-    (the sequential variant of the reference is broken upstream, utils.py:343-363)."""
-    if return_history:
-        raise NotImplementedError("return_history is not on the hot path")
+    (the sequential variant of the reference is broken upstream, utils.py:343-363).
+    return_history: the rollout also records every step's action, scorer.get_score and reward on the device
+    (one eco_env_record launch per step, no host read in the loop) and the returned list gains the reference's
+    `history` frame (columns actions / scores / rewards, one row per graph, each cell one list per attempt)
+    after the raw frame.  Without it the function issues exactly the launches it issued before."""
     dev = torch.device(device) if device is not None else network.flat.device
     rng = np.random.RandomState(seed) if seed is not None else np.random
     reversible = env_args["reversible_spins"]
     n_attempts = n_attempts if reversible else 1
-    results, results_raw = [], []
+    results, results_raw, history = [], [], []
     basis = env_args.get("spin_basis", SpinBasis.SIGNED)
     allowed = 0.0 if basis == SpinBasis.BINARY else -1.0
     for j, test_graph in enumerate(graphs_test):
@@ -125,6 +139,7 @@ def test_network(network, env_args, graphs_test, device=None, step_factor=1, bat
         gcut, gsol = _greedy(genv)
         greedy_single_cut, greedy_single_spins = float(gcut[0]), gsol[0]
         best_solutions, best_spins, init_spins, greedy_cuts, greedy_spins = [], [], [], [], []
+        actions_history, scores_history, rewards_history = [], [], []
         t_total = 0.0
         done_attempts = 0
         while done_attempts < n_attempts:
@@ -139,12 +154,21 @@ def test_network(network, env_args, graphs_test, device=None, step_factor=1, bat
             gids = env.graph_ids
             acts = torch.empty(bsz, dtype=torch.int32, device=dev)
             act = _lib.ActConfig(0.0, int(reversible), allowed, 0, 0)
+            if return_history:   # action, reward and scorer.get_score per step (utils.py:134-137, :158, :189-191)
+                hist = History(env, n_steps + 1, record_solution=False, record_rewards=True, record_qs=False,
+                               record_spins=False, record_score=True, record_mask=False)
+                hist.record(0)
+                skip = torch.empty_like(env.dones)
             torch.cuda.synchronize(dev)
             t0 = time.time()
             scope = _lib.ECO_NORM_PER_CALL  # same batch every step: the call's max degree once, then reused
-            for _ in range(n_steps):
+            for k in range(n_steps):
                 network.forward_graphs(env.obs_x, store, gids, norm_scope=scope, act=act, actions_out=acts)
+                if return_history:
+                    skip.copy_(env.dones)
                 env.step(acts)
+                if return_history:
+                    hist.record(k + 1, skip=skip, actions=acts, rewards=env.rewards)
                 scope = _lib.ECO_NORM_PER_CALL_REUSE
             st = env.read(best_spins=True)
             torch.cuda.synchronize(dev)
@@ -152,6 +176,11 @@ def test_network(network, env_args, graphs_test, device=None, step_factor=1, bat
             best_solutions += list(st["best_solution"].cpu().numpy())
             best_spins += list(st["best_spins"].cpu().numpy().astype(np.float64))
             init_spins += list(spins.astype(np.float64))
+            if return_history:
+                a, sc, r, ln = _history_columns(hist)
+                actions_history += a
+                scores_history += sc
+                rewards_history += r
             if reversible:
                 genv = VecSpinSystem(store, bsz, n_steps, **env_args)
                 genv.reset(graph_ids=np.zeros(bsz, dtype=np.int64), spins=spins)
@@ -171,10 +200,17 @@ def test_network(network, env_args, graphs_test, device=None, step_factor=1, bat
                         greedy_single_cut, greedy_single_spins, greedy_random_cut, greedy_random_spins,
                         greedy_random_mean_cut, t_total / n_attempts])
         results_raw.append([init_spins, best_solutions, best_spins, greedy_cuts, greedy_spins])
+        if return_history:
+            history.append([actions_history, scores_history, rewards_history])
     results = pd.DataFrame(data=results, columns=["cut", "sol", "mean cut", "greedy (+1 init) cut",
                                                   "greedy (+1 init) sol", "greedy (rand init) cut",
                                                   "greedy (rand init) sol", "greedy (rand init) mean cut", "time"])
-    if not return_raw:
+    if not return_raw and not return_history:
         return results
-    results_raw = pd.DataFrame(data=results_raw, columns=["init spins", "cuts", "sols", "greedy cuts", "greedy sols"])
-    return [results, results_raw]
+    ret = [results]
+    if return_raw:
+        ret.append(pd.DataFrame(data=results_raw, columns=["init spins", "cuts", "sols", "greedy cuts",
+                                                             "greedy sols"]))
+    if return_history:   # utils.py:292-302
+        ret.append(pd.DataFrame(data=history, columns=["actions", "scores", "rewards"]))
+    return ret

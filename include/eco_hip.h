@@ -201,6 +201,46 @@ int eco_env_greedy_actions(const eco_env_config *cfg, const eco_graph_set *gs, v
 int eco_env_read(const eco_env_config *cfg, const void *state, int32_t batch, double *scalars, int8_t *spins,
                  int8_t *best_spins, eco_stream_t stream);
 
+/* Trajectory history (Network.history, src/agents/solver.py:189-265; experiments/utils.py:134-207): caller-owned
+ * device buffers of `rows` rows.  Every pointer is optional -- NULL means "do not record", the counterpart of the
+ * reference's record_* flags.  New fields are only ever appended.
+ *   action     f64 [rows][B]      the step's action; 0 on the reset row
+ *   solution   f64 [rows][B]      scorer.get_solution of the current spins
+ *   reward     f64 [rows][B]      the step's reward; 0 on the reset row
+ *   qs         f32 [rows][B][N]   the Q-values the action was chosen from; zeros on the reset row
+ *   spins      i8  [rows][B][N]   env.state[0, :n]: signed +-1 in either spin basis (the basis maps the
+ *                                 observation only, spinsystem.py:567-569)
+ *   score_mask f64 [rows][B][N]   scorer.get_score_mask of the current spins, every vertex (unmasked)
+ *   valid      u8  [rows][B]      scorer.is_valid
+ *   length     i32 [B]            rows written so far for the episode (row + 1)
+ *   score      f64 [rows][B]      scorer.get_score (the per-step column of test_network(return_history=True),
+ *                                 experiments/utils.py:158, :190) */
+typedef struct {
+  int32_t rows;
+  double *action;
+  double *solution;
+  double *reward;
+  float *qs;
+  int8_t *spins;
+  double *score_mask;
+  uint8_t *valid;
+  int32_t *length;
+  double *score;
+} eco_env_history;
+
+/* Append one history row per episode: row 0 is the record Network.reset appends (solver.py:198-216; actions,
+ * rewards and q may be NULL), row >= 1 the record after a step (solver.py:249-265) with the actions[B] stepped,
+ * the rewards[B] returned and the q[B][N] the actions were chosen from.  Episodes with skip[e] != 0 (skip may be
+ * NULL) are left entirely untouched -- their rows and their length; pass the dones held BEFORE the step, so an
+ * episode's last row is the step that finished it (SpinSolver.solve).  One launch, one wave per episode, no
+ * atomics, no host read; reads the env state only.  `gs` is the set the episodes were reset on (read by
+ * MIN_DOM_SET's score mask; may be NULL otherwise).  Float-weighted stores (cfg.float_weights) record float64
+ * values from the f64 local field.  ECO_ERR_ARG before any launch: row outside [0, hist->rows), NULL hist,
+ * B < 1, a float-weighted store with a non-CUT target. */
+int eco_env_record(const eco_env_config *cfg, const eco_graph_set *gs, const void *state, int32_t batch,
+                   int32_t row, const uint8_t *skip, const int32_t *actions, const double *rewards, const float *q,
+                   const eco_env_history *hist, eco_stream_t stream);
+
 /* ---- MPNN Q-network (src/networks/mpnn.py) ---- */
 
 /* Parameter count of MPNN(n_obs_in, n_layers=3, n_features=64, n_hid_readout=[])
