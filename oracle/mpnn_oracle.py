@@ -87,6 +87,53 @@ def forward(w, obs, n_obs_in=7, norm_max=None):
     return q.squeeze()
 
 
+STAGES = ["H0", "H1", "H2", "H3", "E", "EAGG", "M0", "M1", "M2", "AGG0", "AGG1", "AGG2", "MEAN", "P"]
+
+
+def forward_staged(w, x, adj, n_obs_in, norm_max=None):
+    """forward() on node features x [B, N, n_obs_in] and adjacency adj [B, N, N] (the two slices that
+    mpnn.py:47-50 takes of the transposed observation), in the dtype of its inputs throughout: float64 inputs
+    and weights give a float64 forward (forward() forms norm.float() and the nonzero mask in fp32).
+    Returns (Q [B, N], stages): every intermediate under the name of its SV_* slot of the engine's saved
+    activations -- H0..H3 node embeddings (:55, :118), E edge embeddings (:102), EAGG the input of
+    edge_feature_NN (cat([embedded_edges, norm / norm.max()]), :102), M0..M2 messages (:117), AGG0..AGG2
+    aggregated embeddings (:115), MEAN the pooled mean and P layer_pooled of it (:147)."""
+    dt = x.dtype
+    assert x.shape[-1] == n_obs_in and adj.dtype == dt
+    st = {}
+    norm = torch.sum((adj != 0), dim=1).unsqueeze(-1)                 # :36
+    norm = norm.clone()
+    norm[norm == 0] = 1                                               # :37
+    norm = norm.to(dt)                                                # :38
+    h = F.relu(x @ w[KEYS[0]].T)                                      # :20-23, :55
+    st["H0"] = h
+    # EdgeAndNodeEmbeddingLayer (:89-104)
+    B, N = adj.shape[0], adj.shape[1]
+    ef = torch.cat([adj.unsqueeze(-1),
+                    x.unsqueeze(-2).transpose(-2, -3).repeat(1, N, 1, 1)], dim=-1)   # :90-92
+    ef = ef * (adj.unsqueeze(-1) != 0).to(dt)                         # :94
+    emb = F.relu(ef.reshape(B, N * N, -1) @ w[KEYS[1]].T).reshape(B, N, N, -1)       # :96-99
+    emb = emb.sum(dim=2) / norm                                       # :100
+    nmax = norm.max() if norm_max is None else torch.as_tensor(float(norm_max), dtype=norm.dtype,
+                                                                    device=norm.device)
+    st["EAGG"] = torch.cat([emb, norm / nmax], dim=-1)                # :102
+    e = F.relu(st["EAGG"] @ w[KEYS[2]].T)
+    st["E"] = e
+    for i in range(3):                                                # :68-72, :114-120
+        agg = torch.matmul(adj, h) / norm                             # :115
+        m = F.relu(torch.cat([agg, e], dim=-1) @ w[KEYS[3 + 2 * i]].T)    # :117
+        h = F.relu(torch.cat([h, m], dim=-1) @ w[KEYS[4 + 2 * i]].T)      # :118
+        st[f"AGG{i}"], st[f"M{i}"], st[f"H{i + 1}"] = agg, m, h
+    # ReadoutLayer (:143-159)
+    st["MEAN"] = h.sum(dim=1) / N                                     # :147
+    pooled = st["MEAN"] @ w[KEYS[9]].T
+    st["P"] = pooled
+    fp = pooled.unsqueeze(1).expand(B, N, pooled.shape[-1])           # :148
+    feat = F.relu(torch.cat([fp, h], dim=-1))                         # :150
+    q = feat @ w[KEYS[10]].T + w[KEYS[11]]                            # :152-153
+    return q.squeeze(), st
+
+
 def batch_norm_max(states, n_obs_in=7):
     """norm.max() of mpnn.py:102 for a whole batch of observations [B, n_obs_in+N, N]: the largest
     clamped nonzero count of an adjacency row (:36-37)."""
