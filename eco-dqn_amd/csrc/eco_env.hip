@@ -235,12 +235,6 @@ __device__ __forceinline__ void write_obs(const EnvArgs& a, int e, int lane, con
 // float product: s = -1, h = 0 gives -0.0, as the reference's float64 product does).  tests/test_env_gpu.py
 // checks these rows bitwise against the general path.  None of that carries over to float weights (F = double):
 // there s * h / mlr is computed in float64, as the general path does, and rounded once to f32.
-__device__ __forceinline__ bool obs_default_layout(const eco_env_config& c) {
-  return c.n_obs == 7 && c.obs_ids[0] == ECO_OBS_SPIN_STATE && c.obs_ids[1] == ECO_OBS_IMMEDIATE_QUALITY_CHANGE &&
-         c.obs_ids[2] == ECO_OBS_TIME_SINCE_FLIP && c.obs_ids[3] == ECO_OBS_DISTANCE_FROM_BEST_SOLUTION &&
-         c.obs_ids[4] == ECO_OBS_DISTANCE_FROM_BEST_STATE && c.obs_ids[5] == ECO_OBS_NUMBER_OF_QUALITY_IMPROVEMENTS &&
-         c.obs_ids[6] == ECO_OBS_TERMINATION_IMMANENCY;
-}
 template <int VPT, class F>
 __device__ __forceinline__ void write_obs_default(const EnvArgs& a, int e, int lane, const int (&s)[VPT],
                                                   const F (&h)[VPT], const int (&tsf)[VPT], const ObsCtx& c) {

@@ -1155,8 +1155,50 @@ extern "C" int32_t eco_set_kernel_paths(int32_t mask) {
                                          ECO_PATH_DENSE2_FWD));
 }
 
+// The kernel family of one MPNN call (ECO_ROUTE_* of include/eco_hip.h).  The forward, the pair forward and the
+// backward all ask here, and nowhere else are the eligibility predicates and the family bits of ECO_PATH_* read: a
+// training forward writes `saved` in the layout of the family named here, and the backward finds the family that
+// reads it by the same call.  Pure: a function of a.gs (scalar fields, pointer null-ness), a.N, a.gpb, a.xw and
+// the two other arguments.  training: the call writes or reads saved activations (training forward, backward),
+// which no family has above MPNN_MAX_SPINS vertices: ECO_ROUTE_NONE there, and the caller names the limit.
+static int mpnn_route(const MpnnArgs& a, int paths, bool training) {
+  const eco_graph_set* gs = &a.gs;
+  const bool rows8 = a.xw == 8;  // the dense-aggregation families take 8-float observation rows
+  if (rows8 && dense_eligible(gs, a.gpb) && !(paths & ECO_PATH_NO_DENSE))
+    return (paths & ECO_PATH_DENSE2_FWD) ? ECO_ROUTE_DENSE2 : ECO_ROUTE_DENSE3;
+  if (rows8 && dl_eligible(gs, a.gpb) && !(paths & (ECO_PATH_NO_DL | ECO_PATH_NO_DENSE))) return ECO_ROUTE_DL;
+  if (a.N <= MPNN_MAX_SPINS) return ECO_ROUTE_CSR;
+  if (training) return ECO_ROUTE_NONE;  // global-memory embeddings: inference only
+  // one graph shared by every episode (GSet best-cut search): node-major episode-batched kernels
+  if (gs->n_graphs == 1 && gs->unit_weights && !(paths & ECO_PATH_NO_SHARED)) return ECO_ROUTE_SHARED;
+  return ECO_ROUTE_LARGE;
+}
+
+// eco_mpnn_forward_pair runs both networks in ONE launch on one-graph dense blocks with a prepared gs.adjbits;
+// any other pair call is two single forwards of `family`
+static bool pair_fused(const MpnnArgs& a, int family, int paths) {
+  return (family == ECO_ROUTE_DENSE3 || family == ECO_ROUTE_DENSE2) && a.gpb == 1 && a.gs.adjbits &&
+         !(paths & ECO_PATH_NO_PAIR);
+}
+
+extern "C" int32_t eco_mpnn_route(const eco_graph_set* gs, int32_t n_obs_in, int32_t batch, int32_t gpb,
+                                  int32_t training, int32_t pair) {
+  // a call that prepare() rejects has no route
+  if (!gs || n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS || batch < 1 || gs->n_spins < 1 ||
+      gs->n_spins > MPNN_MAX_SPINS_LARGE || (gs->edge_weights && gs->unit_weights))
+    return ECO_ROUTE_NONE;
+  MpnnArgs a{};
+  a.gs = *gs; a.B = batch; a.N = gs->n_spins; a.gpb = gpb > 0 ? gpb : graphs_per_block(a.N, batch);
+  a.xw = ECO_OBS_X_STRIDE(n_obs_in);
+  const int paths = kernel_paths();
+  const int family = mpnn_route(a, paths, training && !pair);  // the pair forward never saves
+  return pair && pair_fused(a, family, paths) ? family | ECO_ROUTE_PAIR_FUSED : family;
+}
+
+// The CSR-gather instantiation of a block: the kernels' MAXT (tiles per wave they are unrolled for; 0: the block
+// is too large for any), waves per workgroup, weights staged in LDS or streamed from L2, dynamic LDS bytes.
 struct KCfg {
-  int nw, maxt;
+  int mt, nw;
   bool wlds;
   size_t lds;
 };
@@ -1176,35 +1218,131 @@ static size_t lds_bytes(int rows_pad, int gpb, int nw, bool wlds, bool backward)
   return f * sizeof(float);
 }
 
-// 8 waves with LDS-staged weights when the block fits, else 4 waves (weights from L2).
+// 16 waves x 1 tile (forward) or 8 waves x 2 or 4 tiles with LDS-staged weights when the block fits, else weights
+// from L2.
 static KCfg pick_cfg(int N, int gpb, bool backward) {
   const int rows_pad = (gpb * N + 15) & ~15;
   const int ntiles = rows_pad / 16;
-  KCfg c;
-  constexpr int force_nw = 0;  // (A/B builds of round 2 forced the wave count here)
+  auto cfg = [&](int nw, bool wlds) { return KCfg{0, nw, wlds, lds_bytes(rows_pad, gpb, nw, wlds, backward)}; };
+  auto tiles = [&](int nw) { return (ntiles + nw - 1) / nw; };  // per wave
   for (int nw : {16, 8, 4}) {
-    if (force_nw && nw != force_nw && nw != 4) continue;
     if (backward && nw == 16) continue;  // the backward's 8-wide weight fragments need > 128 VGPRs
-    c.nw = nw;
-    c.wlds = true;
-    c.lds = lds_bytes(rows_pad, gpb, nw, true, backward);
-    c.maxt = (ntiles + nw - 1) / nw;
-    if (c.lds <= LDS_MAX && c.maxt <= (nw == 16 ? 1 : 4)) return c;
+    KCfg c = cfg(nw, true);
+    if (c.lds <= LDS_MAX && tiles(nw) <= (nw == 16 ? 1 : 4)) {
+      c.mt = nw == 16 ? 1 : (nw == 8 && tiles(nw) <= 2 ? 2 : 4);
+      return c;
+    }
   }
   // weights from L2, 8 waves (2 per SIMD: the block owns the CU through its LDS) when 4 tiles per
   // wave suffice; measured at BA-500: forward 15 % faster than 4 waves x 8 tiles, backward slower
-  if (!force_nw || force_nw == 8) {
-    c.nw = 8;
-    c.wlds = false;
-    c.lds = lds_bytes(rows_pad, gpb, 8, false, backward);
-    c.maxt = (ntiles + 7) / 8;
-    if (c.lds <= LDS_MAX && c.maxt <= 4) return c;
+  KCfg c = cfg(8, false);
+  if (c.lds <= LDS_MAX && tiles(8) <= 4) {
+    c.mt = 4;
+    return c;
   }
-  c.nw = 4;
-  c.wlds = false;
-  c.lds = lds_bytes(rows_pad, gpb, 4, false, backward);
-  c.maxt = (ntiles + 3) / 4;
+  c = cfg(4, false);
+  c.mt = tiles(4) <= 4 ? 4 : (tiles(4) <= 8 ? 8 : 0);
   return c;
+}
+
+// one launch of a kernel with dynamic LDS: its size attribute, then the kernel
+template <class... Args>
+static void launch_lds(void (*kern)(Args...), int blocks, int threads, size_t lds, hipStream_t st, Args... args) {
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  kern<<<blocks, threads, lds, st>>>(args...);
+}
+
+// One row of the CSR-gather table: the forward (saving or not) or the backward of shape (MT, NW, WLDS); fw: the
+// float-weighted instances.  The 16-wave shape has no backward (pick_cfg never returns it for one).
+template <int MT, int NW, bool WL>
+static void launch_csr_row(const KCfg& k, const MpnnArgs& a, bool backward, bool save, hipStream_t st) {
+  const int blocks = (a.B + a.gpb - 1) / a.gpb;
+  const bool fw = a.gs.edge_weights != nullptr;
+  if (!backward) {
+    if (fw && save) launch_lds(mpnn_forward_kernel<MT, true, NW, WL, true>, blocks, 64 * NW, k.lds, st, a);
+    else if (fw) launch_lds(mpnn_forward_kernel<MT, false, NW, WL, true>, blocks, 64 * NW, k.lds, st, a);
+    else if (save) launch_lds(mpnn_forward_kernel<MT, true, NW, WL, false>, blocks, 64 * NW, k.lds, st, a);
+    else launch_lds(mpnn_forward_kernel<MT, false, NW, WL, false>, blocks, 64 * NW, k.lds, st, a);
+  } else if constexpr (NW != 16) {
+    if (fw) launch_lds(mpnn_backward_kernel<MT, NW, WL, true>, blocks, 64 * NW, k.lds, st, a);
+    else launch_lds(mpnn_backward_kernel<MT, NW, WL, false>, blocks, 64 * NW, k.lds, st, a);
+  }
+}
+
+// The CSR-gather launch of a call: the block configuration of pick_cfg, then its row of the table.
+constexpr int cfg_key(int mt, int nw, bool wlds) { return mt * 64 + nw * 2 + (wlds ? 1 : 0); }
+static int launch_csr(const MpnnArgs& a, bool backward, bool save, hipStream_t st) {
+  const KCfg k = pick_cfg(a.N, a.gpb, backward);
+  if (k.lds > LDS_MAX) return fail(ECO_ERR_ARG, "graph block exceeds the LDS budget");
+  switch (cfg_key(k.mt, k.nw, k.wlds)) {
+    case cfg_key(1, 16, true): launch_csr_row<1, 16, true>(k, a, backward, save, st); break;
+    case cfg_key(2, 8, true): launch_csr_row<2, 8, true>(k, a, backward, save, st); break;
+    case cfg_key(4, 8, true): launch_csr_row<4, 8, true>(k, a, backward, save, st); break;
+    case cfg_key(4, 4, true): launch_csr_row<4, 4, true>(k, a, backward, save, st); break;
+    case cfg_key(4, 8, false): launch_csr_row<4, 8, false>(k, a, backward, save, st); break;
+    case cfg_key(4, 4, false): launch_csr_row<4, 4, false>(k, a, backward, save, st); break;
+    case cfg_key(8, 4, false): launch_csr_row<8, 4, false>(k, a, backward, save, st); break;
+    default: return fail(ECO_ERR_ARG, "graph block too large");
+  }
+  return check_launch(backward ? "mpnn_backward" : "mpnn_forward");
+}
+
+// N > 512 inference on the per-episode global-memory kernel: 8 waves, {float weights} x {8-, 16-float rows}
+static int launch_large(const MpnnArgs& a, void* workspace, hipStream_t st) {
+  const int rows_pad = (a.N + 15) & ~15;
+  const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
+  float* hbuf = (float*)((char*)workspace + 256);
+  const bool wide = a.xw == 16;  // more than 8 observables: 16-float rows
+  if (a.gs.edge_weights) {
+    if (wide) launch_lds(mpnn_forward_large_kernel<8, true, 16>, a.B, 512, lds, st, a, hbuf);
+    else launch_lds(mpnn_forward_large_kernel<8, true, 8>, a.B, 512, lds, st, a, hbuf);
+  } else {
+    if (wide) launch_lds(mpnn_forward_large_kernel<8, false, 16>, a.B, 512, lds, st, a, hbuf);
+    else launch_lds(mpnn_forward_large_kernel<8, false, 8>, a.B, 512, lds, st, a, hbuf);
+  }
+  return check_launch("mpnn_forward_large");
+}
+
+// One network of a forward call: its packed weights and where its Q values / actions go.
+struct FwdHead {
+  const float* packed;
+  float* q;
+  const eco_act_config* act;
+  int32_t* actions;
+};
+
+// Per-call set-up of eco_mpnn_forward (n = 1) and eco_mpnn_forward_pair (n = 2): folds ECO_NORM_PER_CALL_REUSE (the
+// workspace already holds the call's max degree) into PER_CALL, validates, fills a[0 .. n) (which differ in P, q,
+// act and actions only) and routes the call.  Unless a pair call falls back to two single forwards (fused false:
+// nothing is launched, they do their own set-up), the call's norm.max() reduction is launched here.
+static int forward_setup(MpnnArgs* a, const FwdHead* h, int n, int32_t n_obs_in, const eco_graph_set* gs,
+                         const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope, void* saved,
+                         void* workspace, hipStream_t st, int& family, bool& fused) {
+  const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;
+  if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
+  if (const int rc = prepare(a[0], h[0].packed, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope)) return rc;
+  if (!workspace) return fail(ECO_ERR_ARG, "null workspace");
+  for (int i = 0; i < n; ++i)
+    if (h[i].act && !h[i].actions) return fail(ECO_ERR_ARG, "act config without actions buffer");
+  for (int i = 0; i < n; ++i)
+    if (!h[i].q && !h[i].act) return fail(ECO_ERR_ARG, "nothing to compute (q and act both null)");
+  a[0].call_maxdeg = (int*)workspace;
+  a[0].sv = (float*)saved;
+  for (int i = n - 1; i >= 0; --i) {
+    a[i] = a[0];
+    a[i].P = h[i].packed;
+    a[i].q = h[i].q;
+    a[i].has_act = h[i].act != nullptr;
+    if (h[i].act) a[i].act = *h[i].act;
+    a[i].actions = h[i].actions;
+  }
+  const int paths = kernel_paths();
+  family = mpnn_route(a[0], paths, saved != nullptr);
+  fused = n == 2 && pair_fused(a[0], family, paths);
+  if (n == 2 && !fused) return ECO_OK;
+  if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg)
+    call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)workspace);
+  return ECO_OK;
 }
 
 extern "C" int eco_mpnn_forward_pair(const float* packed_a, const float* packed_b, int32_t n_obs_in,
@@ -1213,128 +1351,48 @@ extern "C" int eco_mpnn_forward_pair(const float* packed_a, const float* packed_
                                      int32_t* actions_a, float* q_b, const eco_act_config* act_b, int32_t* actions_b,
                                      void* workspace, eco_stream_t stream) {
   if (!packed_b) return fail(ECO_ERR_ARG, "null argument");
-  const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;
-  if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
-  MpnnArgs a;
-  int rc = prepare(a, packed_a, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope);
-  if (rc) return rc;
-  if (!workspace) return fail(ECO_ERR_ARG, "null workspace");
-  if ((act_a && !actions_a) || (act_b && !actions_b)) return fail(ECO_ERR_ARG, "act config without actions buffer");
-  if ((!q_a && !act_a) || (!q_b && !act_b)) return fail(ECO_ERR_ARG, "nothing to compute (q and act both null)");
-  const int paths = kernel_paths();
-  if ((paths & (ECO_PATH_NO_PAIR | ECO_PATH_NO_DENSE)) ||
-      !(a.xw == 8 && dense_eligible(gs, a.gpb) && a.gpb == 1 && gs->adjbits)) {
-    rc = eco_mpnn_forward(packed_a, n_obs_in, gs, graph_ids, batch, obs_x,
-                          reuse_maxdeg ? ECO_NORM_PER_CALL_REUSE : norm_scope, q_a, act_a, actions_a, nullptr,
-                          workspace, stream);
-    if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const FwdHead h[2] = {{packed_a, q_a, act_a, actions_a}, {packed_b, q_b, act_b, actions_b}};
+  MpnnArgs a[2];
+  int family;
+  bool fused;
+  if (const int rc = forward_setup(a, h, 2, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope, nullptr, workspace, st,
+                                   family, fused))
+    return rc;
+  if (!fused) {  // the second forward reuses the first one's call-scope max degree
+    if (const int rc = eco_mpnn_forward(packed_a, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope, q_a, act_a,
+                                        actions_a, nullptr, workspace, stream))
+      return rc;
     return eco_mpnn_forward(packed_b, n_obs_in, gs, graph_ids, batch, obs_x,
                             norm_scope == ECO_NORM_PER_GRAPH ? norm_scope : ECO_NORM_PER_CALL_REUSE, q_b, act_b,
                             actions_b, nullptr, workspace, stream);
   }
-  hipStream_t st = (hipStream_t)stream;
-  int* cmax = (int*)workspace;
-  a.call_maxdeg = cmax;
-  a.sv = nullptr;
-  MpnnArgs b = a;
-  a.q = q_a;
-  a.has_act = act_a != nullptr;
-  if (act_a) a.act = *act_a;
-  a.actions = actions_a;
-  b.P = packed_b;
-  b.q = q_b;
-  b.has_act = act_b != nullptr;
-  if (act_b) b.act = *act_b;
-  b.actions = actions_b;
-  if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg)
-    call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, cmax);
-  if (paths & ECO_PATH_DENSE2_FWD) return mpnn_forward_dense2_pair_launch(a, b, st);
-  return mpnn_forward_dense3_pair_launch(a, b, st);
+  if (family == ECO_ROUTE_DENSE2) return mpnn_forward_dense2_pair_launch(a[0], a[1], st);
+  return mpnn_forward_dense3_pair_launch(a[0], a[1], st);
 }
 
 extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
                                 const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope,
                                 float* q, const eco_act_config* act, int32_t* actions, void* saved, void* workspace,
                                 eco_stream_t stream) {
-  const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;  // the workspace already holds the call max
-  if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
-  MpnnArgs a;
-  int rc = prepare(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope);
-  if (rc) return rc;
-  if (!workspace) return fail(ECO_ERR_ARG, "null workspace");
-  if (act && !actions) return fail(ECO_ERR_ARG, "act config without actions buffer");
-  if (!q && !act) return fail(ECO_ERR_ARG, "nothing to compute (q and act both null)");
   hipStream_t st = (hipStream_t)stream;
-  const int N = a.N;
-  a.q = q;
-  int* cmax = (int*)workspace;
-  a.call_maxdeg = cmax;
-  a.sv = (float*)saved;
-  a.has_act = act != nullptr;
-  if (act) a.act = *act;
-  a.actions = actions;
-  if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg) {
-    call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, cmax);
+  const FwdHead h = {packed, q, act, actions};
+  MpnnArgs a;
+  int family;
+  bool fused;
+  if (const int rc = forward_setup(&a, &h, 1, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope, saved, workspace, st,
+                                   family, fused))
+    return rc;
+  const bool save = saved != nullptr;
+  switch (family) {
+    case ECO_ROUTE_DENSE3: return mpnn_forward_dense3_launch(a, save, st);
+    case ECO_ROUTE_DENSE2: return mpnn_forward_dense2_launch(a, save, st);
+    case ECO_ROUTE_DL: return mpnn_forward_dl_launch(a, save, workspace, st);
+    case ECO_ROUTE_SHARED: return mpnn_forward_shared_launch(a, workspace, st);
+    case ECO_ROUTE_LARGE: return launch_large(a, workspace, st);
+    case ECO_ROUTE_CSR: return launch_csr(a, false, save, st);
+    default: return fail(ECO_ERR_ARG, "training forward (saved activations) supports N <= 512");
   }
-  const int paths = kernel_paths();
-  if (a.xw == 8 && dense_eligible(gs, a.gpb) && !(paths & ECO_PATH_NO_DENSE)) {
-    if (paths & ECO_PATH_DENSE2_FWD) return mpnn_forward_dense2_launch(a, saved != nullptr, st);
-    return mpnn_forward_dense3_launch(a, saved != nullptr, st);
-  }
-  if (a.xw == 8 && dl_eligible(gs, a.gpb) && !(paths & (ECO_PATH_NO_DL | ECO_PATH_NO_DENSE)))
-    return mpnn_forward_dl_launch(a, saved != nullptr, workspace, st);
-  if (N > MPNN_MAX_SPINS) {  // global-memory embeddings: inference only
-    if (saved) return fail(ECO_ERR_ARG, "training forward (saved activations) supports N <= 512");
-    // one graph shared by every episode (GSet best-cut search): node-major episode-batched kernels
-    if (gs->n_graphs == 1 && gs->unit_weights && !(paths & ECO_PATH_NO_SHARED))
-      return mpnn_forward_shared_launch(a, workspace, st);
-    const int rows_pad = (N + 15) & ~15;
-    const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
-#define ECO_LAUNCH_LARGE(FW, XW)                                                                       \
-  do {                                                                                                \
-    (void)hipFuncSetAttribute((const void*)mpnn_forward_large_kernel<8, FW, XW>,                      \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-    mpnn_forward_large_kernel<8, FW, XW><<<batch, 512, lds, st>>>(a, (float*)((char*)workspace + 256)); \
-  } while (0)
-    const bool wide = a.xw == 16;  // more than 8 observables: 16-float rows
-    if (gs->edge_weights) {
-      if (wide) ECO_LAUNCH_LARGE(true, 16);
-      else ECO_LAUNCH_LARGE(true, 8);
-    } else {
-      if (wide) ECO_LAUNCH_LARGE(false, 16);
-      else ECO_LAUNCH_LARGE(false, 8);
-    }
-#undef ECO_LAUNCH_LARGE
-    return check_launch("mpnn_forward_large");
-  }
-  const int blocks = (batch + a.gpb - 1) / a.gpb;
-  const KCfg k = pick_cfg(N, a.gpb, false);
-  if (k.lds > LDS_MAX) return fail(ECO_ERR_ARG, "graph block exceeds the LDS budget");
-  const bool fw = gs->edge_weights != nullptr;
-#define ECO_LAUNCH_FWD(MT, SV, NW, WL, FW)                                                                      \
-  do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)mpnn_forward_kernel<MT, SV, NW, WL, FW>,                            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);                        \
-    mpnn_forward_kernel<MT, SV, NW, WL, FW><<<blocks, 64 * NW, k.lds, st>>>(a);                               \
-  } while (0)
-#define ECO_LAUNCH_FWD2(MT, NW, WL)                                     \
-  do {                                                                 \
-    if (fw && saved) ECO_LAUNCH_FWD(MT, true, NW, WL, true);           \
-    else if (fw) ECO_LAUNCH_FWD(MT, false, NW, WL, true);              \
-    else if (saved) ECO_LAUNCH_FWD(MT, true, NW, WL, false);           \
-    else ECO_LAUNCH_FWD(MT, false, NW, WL, false);                     \
-  } while (0)
-  if (k.wlds && k.nw == 16 && k.maxt <= 1) ECO_LAUNCH_FWD2(1, 16, true);
-  else if (k.wlds && k.nw == 8 && k.maxt <= 2) ECO_LAUNCH_FWD2(2, 8, true);
-  else if (k.wlds && k.nw == 8) ECO_LAUNCH_FWD2(4, 8, true);
-  else if (k.wlds && k.maxt <= 4) ECO_LAUNCH_FWD2(4, 4, true);
-  else if (k.nw == 8 && k.maxt <= 4) ECO_LAUNCH_FWD2(4, 8, false);
-  else if (k.maxt <= 4) ECO_LAUNCH_FWD2(4, 4, false);
-  else if (k.maxt <= 8) ECO_LAUNCH_FWD2(8, 4, false);
-  else return fail(ECO_ERR_ARG, "graph block too large");
-#undef ECO_LAUNCH_FWD2
-#undef ECO_LAUNCH_FWD
-  return check_launch("mpnn_forward");
 }
 
 size_t eco::mpnn_grad_ws_bytes(int32_t n_spins, int32_t batch) {
@@ -1352,39 +1410,16 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
   int rc = prepare(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, ECO_NORM_PER_CALL);
   if (rc) return rc;
   if (!saved || !dq || !gradws) return fail(ECO_ERR_ARG, "null saved/dq/workspace");
-  if (a.N > MPNN_MAX_SPINS) return fail(ECO_ERR_ARG, "MPNN backward supports N <= 512");
   a.sv = (float*)saved;
   a.dq = dq;
   a.gr = (float*)gradws;
-  const int paths = kernel_paths();
-  if (a.xw == 8 && dense_eligible(gs, a.gpb) && !(paths & ECO_PATH_NO_DENSE)) {
-    if (paths & ECO_PATH_DENSE2_FWD) return mpnn_backward_dense2_launch(a, st);
-    return mpnn_backward_dense3_launch(a, st);
+  switch (mpnn_route(a, kernel_paths(), true)) {
+    case ECO_ROUTE_DENSE3: return mpnn_backward_dense3_launch(a, st);
+    case ECO_ROUTE_DENSE2: return mpnn_backward_dense2_launch(a, st);
+    case ECO_ROUTE_DL: return mpnn_backward_dl_launch(a, st);
+    case ECO_ROUTE_CSR: return launch_csr(a, true, false, st);
+    default: return fail(ECO_ERR_ARG, "MPNN backward supports N <= 512");
   }
-  if (a.xw == 8 && dl_eligible(gs, a.gpb) && !(paths & (ECO_PATH_NO_DL | ECO_PATH_NO_DENSE)))
-    return mpnn_backward_dl_launch(a, st);
-  const int blocks = (batch + a.gpb - 1) / a.gpb;
-  const KCfg k = pick_cfg(a.N, a.gpb, true);
-  if (k.lds > LDS_MAX) return fail(ECO_ERR_ARG, "graph block exceeds the LDS budget");
-  const bool fw = gs->edge_weights != nullptr;
-#define ECO_LAUNCH_BWD1(MT, NW, WL, FW)                                                                         \
-  do {                                                                                                         \
-    (void)hipFuncSetAttribute((const void*)mpnn_backward_kernel<MT, NW, WL, FW>,                               \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);                        \
-    mpnn_backward_kernel<MT, NW, WL, FW><<<blocks, 64 * NW, k.lds, st>>>(a);                                  \
-  } while (0)
-#define ECO_LAUNCH_BWD(MT, NW, WL) \
-  do { if (fw) ECO_LAUNCH_BWD1(MT, NW, WL, true); else ECO_LAUNCH_BWD1(MT, NW, WL, false); } while (0)
-  if (k.wlds && k.nw == 8 && k.maxt <= 2) ECO_LAUNCH_BWD(2, 8, true);
-  else if (k.wlds && k.nw == 8) ECO_LAUNCH_BWD(4, 8, true);
-  else if (k.wlds && k.maxt <= 4) ECO_LAUNCH_BWD(4, 4, true);
-  else if (k.nw == 8 && k.maxt <= 4) ECO_LAUNCH_BWD(4, 8, false);
-  else if (k.maxt <= 4) ECO_LAUNCH_BWD(4, 4, false);
-  else if (k.maxt <= 8) ECO_LAUNCH_BWD(8, 4, false);
-  else return fail(ECO_ERR_ARG, "graph block too large");
-#undef ECO_LAUNCH_BWD
-#undef ECO_LAUNCH_BWD1
-  return check_launch("mpnn_backward");
 }
 
 // ---- split2_pk hazard probe (the v_fma_mix inline asm carries its own wait states) ----

@@ -1,26 +1,18 @@
-// Dense-aggregation MPNN forward (src/networks/mpnn.py:40-159) for blocks of <= 224 rows with
-// +-1 edge weights (ER/BA EdgeType.DISCRETE / UNIFORM graphs, N <= 224: ER-20 ... ER-200).
+// Shared helpers of the dense-aggregation MPNN families (eco_mpnn_dense2.h, eco_mpnn_dense3.h: blocks of <= 224
+// rows; eco_mpnn_dl.h: one graph of 224 < N <= 512), all for +-1 edge weights, where every aggregation
 //
-// The CSR gather of eco_mpnn.hip reads one random 256-B embedding row per edge from LDS; 16 lanes
-// of a ds_read_b128 group hit 16 random rows, so at ER-200 density the gather is LDS-bank bound
-// and serialises with the Linears.  Here every aggregation is a dense MFMA product instead:
+//   agg[f][i] = sum_j H[j][f] * A[j][i]      (A symmetric, entries 0/+-1)
 //
-//   agg[f][i] = sum_j H[j][f] * A[j][i]      (A symmetric, entries 0/+-1, exact in bf16)
-//
-// with H split EXACTLY into three bf16 planes H = H1 + H2 + H3 (24 significand bits = fp32), so
-// every product is exact and the sums are fp32 MFMA accumulations: f32-exact products, f32 sums
-// (the reference's own fp32 bmm differs only in summation order).  The planes are stored
-// transposed, HT[p][f][j], so the A-operand fragment (8 consecutive j of one feature) is one
-// 16-B read; the B-operand fragment (8 adjacency entries of one node) is built in registers from
-// a per-row bitmask.  The 16x16 C layout of D[f][node] is exactly the node-operand layout of the
-// f32 Linears (lane: node l&15, features 16c + 4(l>>4) + r), so nothing is transposed.
-//
-// Edge layer (mpnn.py:89-104): with A in {0, +-1}, sum_j [A_ij != 0] relu(We.[A_ij, x_j]) =
-// A+ . relu(Z + w_a) + A- . relu(Z - w_a) (Z = Wx.x per node), two dense products over the same
-// plane buffer.  Linears stay on v_mfma_f32_16x16x4_f32 (exact f32) as in eco_mpnn.hip.
-//
-// One 1024-thread workgroup (16 waves) per block of whole graphs; wave w owns 16-node tile w and
-// keeps that tile's h and e in registers across the layers.
+// is a dense MFMA product over LDS planes of H instead of the CSR gather of eco_mpnn.hip.  This file holds what
+// the families share and no kernel of theirs:
+//   * the eligibility test of the <= 224-row families (dense_eligible) and their size constants (DN_*);
+//   * the plane addressing (plane_off) and the transposed fragment read (tr_read);
+//   * the adjacency operand as per-row bitmasks: gs.adjbits built once per graph (adjbits_kernel,
+//     adjbits_dl_kernel, adjbits_build) or per block in LDS (adj_build, adj_lane, dense_adjacency);
+//   * the ReLU sign masks of the saved activations (pos_mask, masked, store_mask, mask16);
+//   * the LDS-DMA weight-fragment copy (glds_frags) and the 8-input Linear on f32 MFMAs (lin8);
+//   * the exact bf16x3 Linear on weight fragments streamed from L2 (split_frag, mm_bf3_lean), which the CSR-gather
+//     kernels of eco_mpnn.hip use when the weights are not staged in LDS.
 // Included once by eco_mpnn.hip (same translation unit: shares the phase-timing buffer).
 #pragma once
 #include "eco_mpnn.h"
@@ -34,98 +26,31 @@ constexpr int DN_NW = 16;
 constexpr int DN_MAX_ROWS = 224;             // rows_pad limit (14 tiles, 7 k-chunks of 32)
 constexpr int DN_KC = 7;
 constexpr int DN_KPMAX = 224;                // plane rows (nodes j) per feature block
-constexpr int DN_PLANE = 4 * DN_KPMAX * 16;  // bf16 elements per plane: [4 feature blocks][j][16 features]
 constexpr int DN_ADJW = 2 * DN_KC;           // u32 words per adjacency row while it is built: {nz, neg} per chunk
-constexpr int DN_PL_BYTES = 3 * DN_PLANE * 2;
-constexpr int DN_WP_BYTES = 2 * BF_HALF * 2;  // a staged 128-input Linear (48 fragments)
-constexpr int DN_WX_BYTES = BF_HALF * 2;      // prefetched first half of the update Linear
 
 inline bool dense_eligible(const eco_graph_set* gs, int gpb) {
   const int rows_pad = (gpb * gs->n_spins + 15) & ~15;
   return gs->unit_weights && rows_pad <= DN_MAX_ROWS && gs->n_spins >= 4;
 }
 
-inline size_t dense_fwd_lds_bytes(int rows_pad, int gpb) {
-  return (size_t)DN_PL_BYTES + DN_WP_BYTES + DN_WX_BYTES + (size_t)rows_pad * 8 + (size_t)gpb * 12 + 16;
-}
-
-// Plane image: PL[p][ft][j][16] bf16 (feature block ft = f >> 4, 32-B rows); the 8-B piece of features
+// Plane image: PL[p][ft][j][16] 16-bit elements (feature block ft = f >> 4, 32-B rows); the 8-B piece of features
 // 4k .. 4k+3 of row j sits at piece position k ^ ((j >> 2) & 3), so 16 consecutive rows written by one
-// 16-lane group hit 16 distinct bank pairs, and the transposed reads of dense_agg stay conflict-free.
+// 16-lane group hit 16 distinct bank pairs, and the transposed reads of agg2 (eco_mpnn_dense2.h) stay conflict-free.
 __device__ __forceinline__ int plane_off(int ft, int j, int k) {
   return ft * (DN_KPMAX * 16) + j * 16 + 4 * (k ^ ((j >> 2) & 3));
 }
-// store features 16ft + 4k .. +3 of node j as three exact bf16 pieces
-__device__ __forceinline__ void plane_store4(uint16_t* PL, int ft, int j, int k, float4 v) {
-  uint16_t a[4], b[4], c[4];
-  split3_bits(v.x, a[0], b[0], c[0]);
-  split3_bits(v.y, a[1], b[1], c[1]);
-  split3_bits(v.z, a[2], b[2], c[2]);
-  split3_bits(v.w, a[3], b[3], c[3]);
-  const int o = plane_off(ft, j, k);
-  *reinterpret_cast<uint2*>(PL + o) = make_uint2(a[0] | (uint32_t)a[1] << 16, a[2] | (uint32_t)a[3] << 16);
-  *reinterpret_cast<uint2*>(PL + DN_PLANE + o) = make_uint2(b[0] | (uint32_t)b[1] << 16, b[2] | (uint32_t)b[3] << 16);
-  *reinterpret_cast<uint2*>(PL + 2 * DN_PLANE + o) =
-      make_uint2(c[0] | (uint32_t)c[1] << 16, c[2] | (uint32_t)c[3] << 16);
-}
-
 // k-slot order of the aggregation MFMAs: lane group q, element jj <-> node 32kc + 16(jj >> 2) + 4q + (jj & 3)
-// (the rows the two transposed reads of dense_agg deliver).  Per lane and chunk the 8 adjacency entries
+// (the rows the two transposed reads of agg2 deliver).  Per lane and chunk the 8 adjacency entries
 // of those nodes for the lane's node are kept as 16 bits {nz byte, neg byte} (adj_bits16).
 __device__ __forceinline__ uint32_t adj_bits16(uint2 w, int q) {
   const uint32_t nz = ((w.x >> (4 * q)) & 0xFu) | (((w.x >> (16 + 4 * q)) & 0xFu) << 4);
   const uint32_t ng = ((w.y >> (4 * q)) & 0xFu) | (((w.y >> (16 + 4 * q)) & 0xFu) << 4);
   return nz | (ng << 8);
 }
-// B fragment as bf16 0 / +1.0 / -1.0.  MODE 0: A (signed); 1: A+ = [A = +1]; 2: A- = [A = -1].
-template <int MODE>
-__device__ __forceinline__ bf16x8 adj_frag(uint32_t b16) {
-  const uint32_t nz = b16 & 0xFFu, ng = (b16 >> 8) & 0xFFu;
-  const uint32_t on = MODE == 0 ? nz : (MODE == 1 ? (nz & ~ng) : (nz & ng));
-  bf16x8 f;
-#pragma unroll
-  for (int jj = 0; jj < 8; ++jj) {
-    uint32_t v = ((on >> jj) & 1u) ? 0x3F80u : 0u;
-    if (MODE == 0) v |= ((ng >> jj) & 1u) << 15;
-    f[jj] = (short)v;
-  }
-  return f;
-}
-
 typedef short v4s __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ v4s tr_read(const uint16_t* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4s*)(p));
 }
-
-// acc[ft] += sum over k-chunks [kc0, kc1) and the three planes of H[j][16ft + (l&15)] . A^(MODE)[j][node]:
-// acc[ft] = D[16ft + 4q + r][node l&15], the node-operand layout.  A fragments: two ds_read_b64_tr_b16
-// per (plane, ft) -- lane 4q'+p of each 16-lane group addresses row j = 32kc + 4q + q' (+16), piece p.
-// Call with EXEC all ones (wave-uniform conditions only).
-template <int MODE>
-__device__ __forceinline__ void dense_agg(f32x4 (&acc)[4], const uint16_t* PL, const uint32_t (&adjb)[4], int kc0,
-                                          int kc1, int lane) {
-  const int q = lane >> 4;
-  const int j_in = 4 * q + ((lane >> 2) & 3);
-  const int pc = (lane & 3) ^ q;  // piece position: (j >> 2) & 3 == q for every row read here
-#pragma unroll 1
-  for (int kc = kc0; kc < kc1; ++kc) {  // not unrolled: bounds the fragment reads in flight (16-wave VGPR budget)
-    const uint32_t wd = kc < 2 ? adjb[0] : kc < 4 ? adjb[1] : kc < 6 ? adjb[2] : adjb[3];
-    const bf16x8 bf = adj_frag<MODE>((wd >> (16 * (kc & 1))) & 0xFFFFu);
-    const uint16_t* base = PL + (32 * kc + j_in) * 16 + 4 * pc;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int ft = 0; ft < 4; ++ft) {
-        const uint16_t* a = base + p * DN_PLANE + ft * (DN_KPMAX * 16);
-        const v4s lo = tr_read(a), hi = tr_read(a + 16 * 16);
-        const bf16x8 af = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        acc[ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[ft], 0, 0, 0);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float4 as_f4(const f32x4& v) { return make_float4(v[0], v[1], v[2], v[3]); }
 
 // 8 activations of the node-operand layout (float4 c = 2kc and 2kc+1 of a 64-feature block) as the
 // three exact bf16 pieces of a 16x16x32 B fragment (element j <-> feature of bf16_kprime_feature).
@@ -154,31 +79,9 @@ __device__ __forceinline__ void split_frag(const float4& a, const float4& b, bf1
 
 // acc[nt] += W[16nt + ..][one 64-input half] . x  on 16x16x32 bf16 MFMAs with both operands split in
 // three exact bf16 pieces; the six products above 2^-24 relative are kept (W3.X1, W2.X2, W1.X3, W2.X1,
-// W1.X2, W1.X1, smallest first), so each product carries f32 accuracy.  WH: the half's staged
-// fragments [p][nt][kc2] (BF_FRAG bf16 each, lane-linear) in LDS.
-__device__ __forceinline__ void mm_bf3(f32x4 (&acc)[4], const float4 (&x)[4], const uint16_t* WH, int lane) {
-  const uint16_t* wl = WH + lane * 8;
-#pragma unroll
-  for (int kc2 = 0; kc2 < 2; ++kc2) {
-    bf16x8 x1, x2, x3;
-    split_frag(x[2 * kc2], x[2 * kc2 + 1], x1, x2, x3);
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wl + ((0 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(wl + ((1 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      const bf16x8 w3 = *reinterpret_cast<const bf16x8*>(wl + ((2 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3, x1, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x2, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x3, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x1, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x2, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x1, acc[nt], 0, 0, 0);
-    }
-  }
-}
-
-// mm_bf3 with the fragment loads of one output tile at a time in flight (weights streamed from L2 by the
-// CSR-gather kernels, where the register budget, not the load latency, is the constraint)
+// W1.X2, W1.X1, smallest first), so each product carries f32 accuracy.  WH: the half's fragments [p][nt][kc2]
+// (BF_FRAG bf16 each, lane-linear), streamed from L2 by the CSR-gather kernels with the fragment loads of one
+// output tile at a time in flight (there the register budget, not the load latency, is the constraint)
 __device__ __forceinline__ void mm_bf3_lean(f32x4 (&acc)[4], const float4 (&x)[4], const uint16_t* WH, int lane) {
   // opaque to the optimiser: the same fragments are NOT hoisted/CSE'd across the calls of consecutive
   // tiles (which would keep 24 fragments = 96 VGPRs live per Linear half)
@@ -202,34 +105,6 @@ __device__ __forceinline__ void mm_bf3_lean(f32x4 (&acc)[4], const float4 (&x)[4
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x2, acc[nt], 0, 0, 0);
       acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x1, acc[nt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
-// Two output halves (fragment sets WH0, WH1) of one 64-input transposed Linear, sharing the split of x.
-__device__ __forceinline__ void mm_bf3x2(f32x4 (&acc0)[4], f32x4 (&acc1)[4], const float4 (&x)[4],
-                                         const uint16_t* WH0, const uint16_t* WH1, int lane) {
-#pragma unroll
-  for (int kc2 = 0; kc2 < 2; ++kc2) {
-    bf16x8 x1, x2, x3;
-    split_frag(x[2 * kc2], x[2 * kc2 + 1], x1, x2, x3);
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const uint16_t* wl = (hh ? WH1 : WH0) + lane * 8;
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        f32x4& acc = hh ? acc1[nt] : acc0[nt];
-        const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wl + ((0 * 4 + nt) * 2 + kc2) * BF_FRAG);
-        const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(wl + ((1 * 4 + nt) * 2 + kc2) * BF_FRAG);
-        const bf16x8 w3 = *reinterpret_cast<const bf16x8*>(wl + ((2 * 4 + nt) * 2 + kc2) * BF_FRAG);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3, x1, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x3, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x1, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x2, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x1, acc, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);  // bound the fragments in flight (register pressure at 16 waves)
-      }
     }
   }
 }
@@ -438,6 +313,5 @@ __device__ __forceinline__ void lin8(f32x4 (&d)[4], const float* W, float xk0, f
     d[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[nt * 128 + 4], xk1, d[nt], 0, 0, 0);
   }
 }
-
 
 }  // namespace eco

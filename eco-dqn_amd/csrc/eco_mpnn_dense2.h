@@ -719,7 +719,8 @@ __global__ __launch_bounds__(64 * DN_NW, 1) void mpnn_forward_dense2_kernel(Mpnn
   }  // networks
 }
 
-static int dense2_check(const MpnnArgs& a) {
+// launch-time limits of the <= 224-row dense kernels (eco_mpnn_dense3.h launches through it too)
+static int dense_check(const MpnnArgs& a) {
   const int rows_pad = (a.gpb * a.N + 15) & ~15;
   if (rows_pad > DN_MAX_ROWS || a.gpb > D2_MAX_GPB) return fail(ECO_ERR_ARG, "dense MPNN block exceeds the LDS tables");
   if (readout_scratch_floats(rows_pad, a.gpb, DN_NW, false) * 4 > D2_WBUF_BYTES)
@@ -728,7 +729,7 @@ static int dense2_check(const MpnnArgs& a) {
 }
 
 static int mpnn_forward_dense2_launch(const MpnnArgs& a, bool save, hipStream_t st) {
-  if (const int rc = dense2_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   const int blocks = (a.B + a.gpb - 1) / a.gpb;
   if (save) mpnn_forward_dense2_kernel<true, 1><<<blocks, 64 * DN_NW, 0, st>>>(a, a);
   else mpnn_forward_dense2_kernel<false, 1><<<blocks, 64 * DN_NW, 0, st>>>(a, a);
@@ -736,7 +737,7 @@ static int mpnn_forward_dense2_launch(const MpnnArgs& a, bool save, hipStream_t 
 }
 // two networks on the same graphs and features in one launch (a and b differ only in P, q, act, actions)
 static int mpnn_forward_dense2_pair_launch(const MpnnArgs& a, const MpnnArgs& b, hipStream_t st) {
-  if (const int rc = dense2_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   if (a.gpb != 1) return fail(ECO_ERR_ARG, "paired dense forward: one graph per block only");
   mpnn_forward_dense2_kernel<false, 2><<<a.B, 64 * DN_NW, 0, st>>>(a, b);
   return check_launch("mpnn_forward_dense2_pair");
@@ -1091,7 +1092,7 @@ __global__ __launch_bounds__(64 * DN_NW, 1) void mpnn_backward_dense2_kernel(Mpn
 }
 
 static int mpnn_backward_dense2_launch(const MpnnArgs& a, hipStream_t st) {
-  if (const int rc = dense2_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   const int blocks = (a.B + a.gpb - 1) / a.gpb;
   mpnn_backward_dense2_kernel<<<blocks, 64 * DN_NW, 0, st>>>(a);
   return check_launch("mpnn_backward_dense2");

@@ -784,19 +784,11 @@ __global__ __launch_bounds__(64 * D3_NW, 1) void mpnn_forward_dense3_kernel(Mpnn
   if constexpr (NNET == 2) net_body(a1, nullptr, false);
 }
 
-static int dense3_check(const MpnnArgs& a) {
-  const int rows_pad = (a.gpb * a.N + 15) & ~15;
-  if (rows_pad > DN_MAX_ROWS || a.gpb > D2_MAX_GPB) return fail(ECO_ERR_ARG, "dense MPNN block exceeds the LDS tables");
-  if (readout_scratch_floats(rows_pad, a.gpb, DN_NW, false) * 4 > D2_WBUF_BYTES)
-    return fail(ECO_ERR_ARG, "dense MPNN readout scratch exceeds its buffer");
-  return ECO_OK;
-}
-
 // the staging path of the launch (one graph per block with a prepared gs.adjbits: per-lane loads) as a template
 // argument: a run-time branch merged the two paths' registers and turned every staging wait into vmcnt(0)
 inline bool mpnn_dense3_prep(const MpnnArgs& a) { return a.gpb == 1 && a.gs.adjbits != nullptr; }
 static int mpnn_forward_dense3_launch(const MpnnArgs& a, bool save, hipStream_t st) {
-  if (const int rc = dense3_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   const int blocks = (a.B + a.gpb - 1) / a.gpb;
   const bool prep = mpnn_dense3_prep(a);
   if (save && prep) mpnn_forward_dense3_kernel<true, 1, true><<<blocks, 64 * D3_NW, 0, st>>>(a, a);
@@ -806,7 +798,7 @@ static int mpnn_forward_dense3_launch(const MpnnArgs& a, bool save, hipStream_t 
   return check_launch("mpnn_forward_dense3");
 }
 static int mpnn_forward_dense3_pair_launch(const MpnnArgs& a, const MpnnArgs& b, hipStream_t st) {
-  if (const int rc = dense3_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   if (a.gpb != 1) return fail(ECO_ERR_ARG, "paired dense forward: one graph per block only");
   if (mpnn_dense3_prep(a)) mpnn_forward_dense3_kernel<false, 2, true><<<a.B, 64 * D3_NW, 0, st>>>(a, b);
   else mpnn_forward_dense3_kernel<false, 2, false><<<a.B, 64 * D3_NW, 0, st>>>(a, b);
@@ -1262,7 +1254,7 @@ __global__ __launch_bounds__(64 * D3_NW, 1) void mpnn_backward_dense3_kernel(Mpn
 }
 
 static int mpnn_backward_dense3_launch(const MpnnArgs& a, hipStream_t st) {
-  if (const int rc = dense3_check(a)) return rc;
+  if (const int rc = dense_check(a)) return rc;
   const int blocks = (a.B + a.gpb - 1) / a.gpb;
   if (mpnn_dense3_prep(a)) mpnn_backward_dense3_kernel<true><<<blocks, 64 * D3_NW, 0, st>>>(a);
   else mpnn_backward_dense3_kernel<false><<<blocks, 64 * D3_NW, 0, st>>>(a);

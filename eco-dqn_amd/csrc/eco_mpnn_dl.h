@@ -30,7 +30,6 @@ namespace eco {
 constexpr int DL_NW = DL_NW_X;                    // waves per workgroup
 constexpr int DL_MT = DL_MT_X;                    // 16-node tiles per wave
 constexpr int DL_MAX_ROWS = DL_NW * DL_MT * 16;   // 512
-constexpr int DL_KC = DL_MAX_ROWS / 32;           // k-chunks of 32 nodes
 constexpr int DL_AW = 8;                          // adjacency words per (node, lane quarter): 16 chunks x 16 bits
 constexpr int DL_PLANE = 2 * DL_MAX_ROWS * 16;    // fp16 per plane: [2 feature blocks][512 rows][16] = 32 KB
 static_assert(DL_PLANE == D2_WBUF, "a V plane fills one Linear buffer");
@@ -49,7 +48,7 @@ inline bool dl_eligible(const eco_graph_set* gs, int gpb) {
   return gs->unit_weights && gs->adjbits != nullptr && gpb == 1 && rows_pad > DN_MAX_ROWS && rows_pad <= DL_MAX_ROWS;
 }
 
-// plane image of one feature half: [feature block ftl][row j][16] with the 8-B piece swizzle of plane_off
+// plane image of one feature half: [feature block ftl][row j][16] with the 8-B piece swizzle of plane_off (eco_mpnn_dense.h)
 __device__ __forceinline__ int dl_plane_off(int ftl, int j, int k) {
   return ftl * (DL_MAX_ROWS * 16) + j * 16 + 4 * (k ^ ((j >> 2) & 3));
 }

@@ -147,32 +147,9 @@ __device__ __forceinline__ void st4_nt(float* p, float4 x) {
   __builtin_nontemporal_store(v4{x.x, x.y, x.z, x.w}, reinterpret_cast<v4*>(p));
 }
 
-// mm_bf3 over LDS fragments with one output tile's fragments in flight at a time (the shared-graph layer
-// runs four Linears back to back: unbounded, the compiler hoists all 96 fragment reads and spills)
-__device__ __forceinline__ void mm_bf3_seq(f32x4 (&acc)[4], const float4 (&x)[4], const uint16_t* WH, int lane) {
-  const uint16_t* wl = WH + lane * 8;
-#pragma unroll
-  for (int kc2 = 0; kc2 < 2; ++kc2) {
-    bf16x8 x1, x2, x3;
-    split_frag(x[2 * kc2], x[2 * kc2 + 1], x1, x2, x3);
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-      const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wl + ((0 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(wl + ((1 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      const bf16x8 w3 = *reinterpret_cast<const bf16x8*>(wl + ((2 * 4 + nt) * 2 + kc2) * BF_FRAG);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3, x1, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x2, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x3, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, x1, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x2, acc[nt], 0, 0, 0);
-      acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, x1, acc[nt], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-}
-
 // mm_fh of eco_mpnn_dense2.h (fp16x2 operands: the 64-input half of x scaled by the node's 2^kx, hi / lo pieces, three
-// products) with one output tile's fragments in flight at a time, for the same reason as mm_bf3_seq
+// products) with one output tile's fragments in flight at a time (the shared-graph layer runs four Linears back to
+// back: unbounded, the compiler hoists all the fragment reads and spills)
 __device__ __forceinline__ void mm_fh_seq(f32x4 (&acc)[4], const float4 (&x)[4], float sf, const uint16_t* WH,
                                           int lane) {
   const uint16_t* wl = WH + lane * 8;
@@ -259,14 +236,6 @@ __global__ __launch_bounds__(256) void shared_perm_kernel(MpnnArgs a, SharedBufs
   r += __shfl_xor(r, 1, 64);
   r += __shfl_xor(r, 2, 64);
   if (i < N && part == 0) sb.perm[r] = i;
-}
-
-// chunk c (features 16c .. 16c+15) of an 8-input Linear (W0 or Wx) for the lane's node l & 15: exactly the
-// d[c] of lin8 (the same two MFMAs), so h0 / U / V rebuilt here equal those of the dense kernels' form
-__device__ __forceinline__ f32x4 lin8_chunk(const float* W, int c, float xk0, float xk1, int lane) {
-  const float* wl = W + (lane & 15) * 8 + (lane >> 4);
-  const f32x4 d = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[c * 128], xk0, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(wl[c * 128 + 4], xk1, d, 0, 0, 0);
 }
 
 // The 16-input form of lin8 (observation rows of 16 floats, n_obs_in > 8): the two K-steps of lin8 on W [64][8]
@@ -436,7 +405,8 @@ __global__ __launch_bounds__(SP_THREADS) void shared_pack_kernel(SharedBufs sb) 
 // mode 0: weight w (+-1); +1: edges with w > 0, weight 1; -1: edges with w < 0, weight 1.  accumulate: add
 // to AG (the A- pass of the edge phase).
 // XSRC 0: the block is read from src; 1 / 2 / 3: it is BUILT from the observation rows x (32 B per node) as
-// U = relu(Wx.x + w_a) / V = relu(Wx.x - w_a) / h0 = relu(W0.x) (mpnn.py:89-104, :55) with lin8_chunk: the
+// U = relu(Wx.x + w_a) / V = relu(Wx.x - w_a) / h0 = relu(W0.x) (mpnn.py:89-104, :55) with lin8's two MFMAs per
+// 16-feature chunk (d[c] of lin8, eco_mpnn_dense.h, so the rebuilt rows equal those of the dense kernels' form): the
 // next item's x values are what is prefetched, the Linear runs when the block is written to LDS.
 // XW: floats per observation row (XSRC 1..3).  16 (n_obs_in > 8): two more x values per tile are prefetched and the
 // build runs four K-steps (lin16's order), its weight block AG_WL16 floats; the 8-wide instances are unchanged.
@@ -445,7 +415,6 @@ constexpr int AG_WL = 576;                                        // floats of t
 // 16-float observation rows (XW = 16): the weights of features 8..15 (64 x 8: PK_W0H / PK_WXH) follow the AG_WL block
 constexpr int AG_WL16 = AG_WL + 512;
 constexpr int AG_PF = (4096 + 64 * AG_NW - 1) / (64 * AG_NW);  // float4 per thread per block: 64 KB (N <= 2048)
-constexpr int AG_XT = (2048 / 16 + AG_NW - 1) / AG_NW;          // 16-node x tiles per wave (N <= 2048)
 // A wave's tile pairs are the same for every item: p = w + (r AG_TPW + j) AG_NW, rounds r < AG_R.  Their row
 // lengths, table offsets and output nodes are read once per workgroup into registers (global loads inside the item
 // loop would wait for the next block's prefetch too: vmcnt counts in order).
@@ -572,7 +541,7 @@ __global__ __launch_bounds__(64 * NW, 1) void shared_agg_kernel(MpnnArgs a, Shar
   const int n2 = N * 2;
   static_assert(XSRC != 0 || NW == AG_NW, "AG_PF is sized for AG_NW waves");
   constexpr int NPF = XSRC ? 1 : AG_PF;
-  constexpr int NXT = XSRC ? (2048 / 16 + NW - 1) / NW : 1;  // 16-node x tiles per wave (AG_XT at AG_NW waves)
+  constexpr int NXT = XSRC ? (2048 / 16 + NW - 1) / NW : 1;  // 16-node x tiles per wave (N <= 2048)
   float4 pf[NPF];
   float xk0[NXT], xk1[NXT];
   float xk2[XW == 16 ? NXT : 1], xk3[XW == 16 ? NXT : 1];  // features 8..15 (wide rows)
@@ -629,7 +598,7 @@ __global__ __launch_bounds__(64 * NW, 1) void shared_agg_kernel(MpnnArgs a, Shar
         if (i < n2) HL[i] = pf[u];
       }
     } else {
-      // lin8_chunk gives features 16 (pc / 2) + 4 (ln >> 4) ..: the lanes of 8-feature chunk pc keep theirs
+      // chunk c of lin8 gives features 16c + 4 (ln >> 4) .. (c = pc / 2): the lanes of 8-feature chunk pc keep theirs
       const bool mine = (ln >> 5) == (pc & 1);
       const float* wl = WLs + (ln & 15) * 8 + (ln >> 4) + (pc >> 1) * 128;
       const float wv0 = wl[0], wv1 = wl[4];
@@ -644,7 +613,7 @@ __global__ __launch_bounds__(64 * NW, 1) void shared_agg_kernel(MpnnArgs a, Shar
       for (int j = 0; j < NXT; ++j) {
         const int n = (wv_ + j * NW) * 16 + (ln & 15);
         if ((wv_ + j * NW) * 16 >= N) break;  // wave-uniform: MFMAs below run with EXEC all ones
-        // lin8_chunk on the preloaded weights (the same two MFMAs)
+        // lin8's chunk on the preloaded weights (the same two MFMAs)
         f32x4 z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv0, xk0[j], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         z = __builtin_amdgcn_mfma_f32_16x16x4f32(wv1, xk1[j], z, 0, 0, 0);
         if constexpr (XW == 16) {  // features 8..15: lin16's third and fourth K-step

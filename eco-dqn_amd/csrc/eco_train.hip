@@ -42,7 +42,7 @@ struct WJobs {
 
 // Same reduction on 32x32x16 bf16 MFMAs: dY and X are split EXACTLY into three bf16 pieces while a
 // 32-row tile is staged (split3_bits), and the six products above 2^-24 relative are accumulated in
-// f32 (as mm_bf3 does for the forward Linears), so the sums keep f32 accuracy at ~2.7x the f32-MFMA
+// f32 (as mm_bf3_lean does for the forward Linears), so the sums keep f32 accuracy at ~2.7x the f32-MFMA
 // rate.  Staging transposes through registers: thread t loads column (t & 63) of 8 consecutive rows
 // (each wave-level load is one contiguous 256-B row segment), splits, and writes the three 8-row
 // pieces as 16-B LDS stores into [p][column][row] planes, which are exactly the MFMA fragments

@@ -36,6 +36,10 @@ ECO_WEIGHTS_UNIFORM, ECO_WEIGHTS_DISCRETE, ECO_WEIGHTS_RANDOM = 0, 1, 2   # eco_
 ECO_LOSS_MSE, ECO_LOSS_HUBER = 0, 1   # eco_dqn_td_loss loss kinds
 # kernel-path policy bits (eco_set_kernel_paths)
 ECO_PATH_NO_DENSE, ECO_PATH_NO_DL, ECO_PATH_NO_SHARED, ECO_PATH_NO_PAIR, ECO_PATH_DENSE2_FWD = 1, 2, 4, 8, 16
+# kernel families (eco_mpnn_route); PAIR_FUSED is or-ed in when a pair call runs both networks in one launch
+ECO_ROUTE_NONE, ECO_ROUTE_DENSE3, ECO_ROUTE_DENSE2, ECO_ROUTE_DL, ECO_ROUTE_SHARED, ECO_ROUTE_LARGE, \
+    ECO_ROUTE_CSR = range(7)
+ECO_ROUTE_PAIR_FUSED = 16
 
 
 class EnvConfig(ctypes.Structure):
@@ -96,6 +100,7 @@ _SIG = {
     "eco_check_errors": (ctypes.c_int, [_P]),
     "eco_error_word_copy": (ctypes.c_int, [_P, _P]),
     "eco_set_kernel_paths": (_I, [_I]),
+    "eco_mpnn_route": (_I, [ctypes.POINTER(GraphSet), _I, _I, _I, _I, _I]),
     "eco_probe_split2_mfma": (ctypes.c_int, [_P, _P, _P, _I, _I, _P, _P]),
     "eco_env_greedy_actions": (ctypes.c_int, [ctypes.POINTER(EnvConfig), ctypes.POINTER(GraphSet), _P, _I, _P,
                                               _P]),

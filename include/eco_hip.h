@@ -318,6 +318,25 @@ int eco_mpnn_forward_pair(const float *packed_a, const float *packed_b, int32_t 
 enum { ECO_PATH_NO_DENSE = 1, ECO_PATH_NO_DL = 2, ECO_PATH_NO_SHARED = 4, ECO_PATH_NO_PAIR = 8, ECO_PATH_DENSE2_FWD = 16 };
 int32_t eco_set_kernel_paths(int32_t mask);
 
+/* Which kernel family the MPNN dispatcher picks under the current eco_set_kernel_paths mask (no reference
+ * counterpart: src/networks/mpnn.py:40-159 is one forward; the families compute it for different shapes).  Host
+ * only: nothing is launched and no device memory is read -- of *gs only the scalar fields and whether adjbits and
+ * edge_weights are NULL.  n_obs_in and batch as for eco_mpnn_forward; graphs_per_block: graphs per workgroup
+ * block, <= 0 for the library's own choice (which asks the device for its compute-unit count); training != 0: a
+ * forward with `saved`, or eco_mpnn_backward (the two always agree); pair != 0: eco_mpnn_forward_pair (which never
+ * saves: training is ignored).  Returns the family of the call:
+ *   DENSE3 / DENSE2 -- dense aggregation, blocks of <= 224 rows (DENSE2 under ECO_PATH_DENSE2_FWD);
+ *   DL     -- dense aggregation, one graph of 224 < N <= 512 per workgroup;
+ *   CSR    -- CSR gathers from LDS-resident embeddings, N <= 512;
+ *   SHARED -- N > 512, every episode on one shared graph;   LARGE -- N > 512, embeddings in global memory;
+ *   NONE   -- the call would be rejected (bad arguments, or training above 512 vertices).
+ * For a pair call ECO_ROUTE_PAIR_FUSED is or-ed in when both networks run in one launch; without it the pair runs
+ * as two eco_mpnn_forward calls of the family returned. */
+enum { ECO_ROUTE_NONE = 0, ECO_ROUTE_DENSE3 = 1, ECO_ROUTE_DENSE2 = 2, ECO_ROUTE_DL = 3, ECO_ROUTE_SHARED = 4,
+       ECO_ROUTE_LARGE = 5, ECO_ROUTE_CSR = 6, ECO_ROUTE_PAIR_FUSED = 16 };
+int32_t eco_mpnn_route(const eco_graph_set *gs, int32_t n_obs_in, int32_t batch, int32_t graphs_per_block,
+                       int32_t training, int32_t pair);
+
 /* Test probe of the fp16x2 operand split (no reference counterpart; guards the dense kernels' inline-asm
  * v_fma_mix split, which carries its own MFMA wait states -- src/networks/mpnn.py:111-118 is the Linear it feeds).
  * n_blocks blocks of 64 nodes x 16 fp32 activations x[n_blocks][64][16], per-block power-of-two scale sf[n_blocks],

@@ -38,6 +38,13 @@ def _scaled(a, b):
     return e
 
 
+def _route(store, B, training=0, pair=0):
+    """eco_mpnn_route: the family the dispatcher picks for this store and batch under the current mask (host only)."""
+    import ctypes
+    from eco_hip import _lib
+    return _lib.lib.eco_mpnn_route(ctypes.byref(store.gs), 7, B, 0, training, pair)
+
+
 def _rel(a, b):
     e = float((a - b).norm() / b.norm().clamp_min(1e-30))
     print(f"rel L2 {e:.3e}")
@@ -58,6 +65,7 @@ def test_no_dl_matches_dense_large_kernels():
     out = {}
     for mask in (0, _lib.ECO_PATH_NO_DL):
         with _lib.kernel_paths(mask):
+            assert _route(store, B) == _route(store, B, training=1) == (_lib.ECO_ROUTE_CSR if mask else _lib.ECO_ROUTE_DL)
             q = net.forward_graphs(x, store, gids, norm_scope=_lib.ECO_NORM_PER_GRAPH).clone()
             saved = torch.empty(MPNN.saved_bytes(n, B), dtype=torch.uint8, device="cuda")
             qs = net.forward_graphs(x, store, gids, norm_scope=_lib.ECO_NORM_PER_CALL, saved=saved).clone()
@@ -90,6 +98,7 @@ def test_no_shared_matches_shared_graph_kernels():
     res = {}
     for mask in (0, _lib.ECO_PATH_NO_SHARED):
         with _lib.kernel_paths(mask):
+            assert _route(one, B) == (_lib.ECO_ROUTE_LARGE if mask else _lib.ECO_ROUTE_SHARED)
             q = torch.empty(B, n, device="cuda")
             a = torch.empty(B, dtype=torch.int32, device="cuda")
             net.forward_graphs(x, one, gz, norm_scope=_lib.ECO_NORM_PER_CALL, q_out=q,
@@ -117,6 +126,9 @@ def test_pair_paths(bit):
     mask = getattr(_lib, "ECO_PATH_" + bit)
     for m in (0, mask):
         with _lib.kernel_paths(m):
+            assert _route(store, B, pair=1) == {0: _lib.ECO_ROUTE_DENSE3 | _lib.ECO_ROUTE_PAIR_FUSED,
+                                                _lib.ECO_PATH_NO_PAIR: _lib.ECO_ROUTE_DENSE3,
+                                                _lib.ECO_PATH_NO_DENSE: _lib.ECO_ROUTE_CSR}[m]
             a = torch.empty(B, dtype=torch.int32, device="cuda")
             qb = torch.empty(B, n, device="cuda")
             net.forward_pair_graphs(tgt, x, store, gids, norm_scope=_lib.ECO_NORM_PER_CALL, act=greedy,
