@@ -9,7 +9,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int MPNN_MAX_SPINS = 512;  // block of one graph must fit LDS (rows_pad * 272 B + scratch)
-constexpr int MPNN_MAX_SPINS_LARGE = ECO_MAX_SPINS;  // global-memory embeddings (inference only) above 512
+constexpr int MPNN_MAX_SPINS_LARGE = ECO_MAX_SPINS;  // global-memory embeddings above 512 (inference; eco_mpnn_grad_large)
 constexpr int LDH = 72;              // LDS row stride (floats) of 64-wide tiles: = 8 (mod 64) makes the MFMA
                                      // operand reads (16 rows x 4 quads per ds_read_b128 lane group) conflict-free
 constexpr int LDW = 136;             // LDS row stride of staged [64][128] weights (same property)
@@ -174,5 +174,15 @@ size_t mpnn_grad_ws_bytes(int32_t n_spins, int32_t batch);
 int mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
                          int32_t batch, const float* obs_x, const void* saved, const float* dq, void* gradws,
                          hipStream_t st);
+
+// eco_mpnn_grad_large (512 < N <= 2048): byte offsets of the parts of its workspace, and the launches that fill
+// the saved activations and the gradient workspace inside it (eco_train.hip adds the weight-gradient tail)
+struct GradLargeLayout {
+  size_t sv, gr, g, hbuf, slabs, total;  // total = 0: unsupported size
+};
+GradLargeLayout mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes);
+int mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
+                           int32_t batch, const float* obs_x, const float* dq, void* workspace,
+                           const GradLargeLayout& L, hipStream_t st);
 
 }  // namespace eco

@@ -869,7 +869,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
 }
 
 // ======================================================== large graphs ====
-// N > 512 (GSet G22, N = 2000; inference / best-cut search only): the node embeddings no longer fit
+// N > 512 (GSet G22, N = 2000; inference / best-cut search, and the forward inside eco_mpnn_grad_large): the node embeddings no longer fit
 // LDS, so each episode's Z / h rows live in global memory (two ping-pong [rows][64] f32 buffers and the
 // edge embedding e, in the forward workspace: per episode 3 x rows x 256 B, L2/MALL-resident while the
 // workgroup runs).  One workgroup per episode; waves take 16-node tiles round-robin; the
@@ -880,7 +880,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_backw
 // XW: floats per observation row, 8 or 16 (n_obs_in > 8, MAIN_OBSERVABLES).  The wide instance adds features
 // 8..15 to the two 8-input Linears from PK_WXH / PK_W0H in the summation order of mpnn_forward_kernel's xdot_hi:
 // the low eight products, then the high eight as one term.
-template <int NW, bool FW = false, int XW = 8>
+// SAVE: the forward inside eco_mpnn_grad_large -- every activation mpnn_backward_large_kernel and the weight-gradient
+// jobs read goes to a.sv ([tensor][B N][64], the layout of the N <= 512 training forward) at the point it exists in
+// registers, MEAN and P through readout_act<true>.  The non-saving instances are unchanged by the parameter.
+template <int NW, bool FW = false, int XW = 8, bool SAVE = false>
 __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs a, float* hbuf) {
   static_assert(XW == 8 || XW == 16, "observation rows are 8 or 16 floats");
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -975,12 +978,24 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[c] = zero4();
       }
+      if constexpr (SAVE) {
+        if (valid) {
+          float* ea = a.sv + (size_t)SV_EAGG * RT * 64 + (R0 + r) * 64 + 4 * s4;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) st4(ea + 16 * c, acc[c]);
+        }
+      }
       f32x4 d[4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
       mm_bf3_lean(d, acc, BFP + BF_WF, lane);
 #pragma unroll
-      for (int nt = 0; nt < 4; ++nt) st4(EB + (size_t)r * 64 + 16 * nt + 4 * s4, relu4(d[nt]));
+      for (int nt = 0; nt < 4; ++nt) {
+        st4(EB + (size_t)r * 64 + 16 * nt + 4 * s4, relu4(d[nt]));
+        if constexpr (SAVE) {
+          if (valid) st4(a.sv + (size_t)SV_E * RT * 64 + (R0 + r) * 64 + 16 * nt + 4 * s4, relu4(d[nt]));
+        }
+      }
     }
     float w0[8];
 #pragma unroll
@@ -1002,6 +1017,9 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
                     w0[6] * x1.z + w0[7] * x1.w);
       }
       HA[(size_t)r * 64 + lane] = h0;
+      if constexpr (SAVE) {
+        if (r < N) a.sv[(size_t)SV_H0 * RT * 64 + (R0 + r) * 64 + lane] = h0;
+      }
     }
   }
   __threadfence();
@@ -1036,6 +1054,13 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
         am[c].x = am[c].x / nf; am[c].y = am[c].y / nf; am[c].z = am[c].z / nf; am[c].w = am[c].w / nf;
         ev[c] = f4(EB + (size_t)r * 64 + 16 * c + 4 * s4);
       }
+      if constexpr (SAVE) {
+        if (valid) {
+          float* sa = a.sv + (size_t)(SV_AGG0 + layer) * RT * 64 + (R0 + r) * 64 + 4 * s4;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) st4(sa + 16 * c, am[c]);
+        }
+      }
       f32x4 d[4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) d[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1047,6 +1072,13 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
         hc[c] = f4(Hc + (size_t)r * 64 + 16 * c + 4 * s4);
         mr[c] = relu4(d[c]);
       }
+      if constexpr (SAVE) {
+        if (valid) {
+          float* sm = a.sv + (size_t)(SV_M0 + layer) * RT * 64 + (R0 + r) * 64 + 4 * s4;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) st4(sm + 16 * c, mr[c]);
+        }
+      }
       f32x4 hn[4];
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) hn[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1054,6 +1086,13 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
       mm_bf3_lean(hn, mr, BFL + 3 * BF_HALF, lane);
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) st4(Hn + (size_t)r * 64 + 16 * nt + 4 * s4, valid ? relu4(hn[nt]) : zero4());
+      if constexpr (SAVE) {
+        if (valid) {
+          float* sh = a.sv + (size_t)(SV_H0 + layer + 1) * RT * 64 + (R0 + r) * 64 + 4 * s4;
+#pragma unroll
+          for (int nt = 0; nt < 4; ++nt) st4(sh + 16 * nt, relu4(hn[nt]));
+        }
+      }
     }
     __threadfence();  // release the Hn rows and invalidate this CU's L1 before other waves read them
     __syncthreads();  // every wave done with Hc; Hn complete
@@ -1062,7 +1101,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
     Hn = tmp;
   }
   // ---- phase E: readout + act over the h3 rows in global memory ----
-  readout_act<false, NW>(a, Hc, 64, Scr, true, e, 1, N, R0, RT);
+  readout_act<SAVE, NW>(a, Hc, 64, Scr, true, e, 1, N, R0, RT);
 }
 
 // norm.max() of the call (mpnn.py:102 over every graph of the batch): ONE workgroup reduces all B graph
@@ -1079,6 +1118,304 @@ __global__ __launch_bounds__(1024) void call_maxdeg_kernel(const eco_graph_set g
     int r = red[0];
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = max(r, red[w]);
     *out = r;
+  }
+}
+
+// Backward over global-memory rows (512 < N <= 2048): mpnn_backward_kernel restated for one workgroup per episode,
+// the saved activations a.sv of mpnn_forward_large_kernel<.., SAVE = true> and the gradient workspace a.gr in the
+// layout of mpnn_grad_ws_bytes (graphs_per_block is 1 here: one DWA row per episode).  Waves own 16-node tiles
+// round-robin (t = w; t += NW), the same tiles in every phase, so a row of GR_DH or GR_DE is only ever read by the
+// thread that wrote it.  What the LDS kernel keeps in its array G (the rows other waves gather from) is the
+// episode's [rows_pad][64] buffer in gbuf, with the forward's fence + barrier pair between writing and gathering;
+// dh lives in the GR_DH rows instead of per-tile registers.  The Linears are the bf16x3 transposed fragments from
+// L2 (the WLDS = false branch).  No atomics: every reduction runs in a fixed order.
+// LDS: DQ [rows_pad] | DMEAN [64] | RED [NW][64]
+template <int NW, bool FW = false>
+__global__ __launch_bounds__(64 * NW, 1) void mpnn_backward_large_kernel(MpnnArgs a, float* gbuf) {
+  __shared__ float DQ[MPNN_MAX_SPINS_LARGE];
+  __shared__ float DMEAN[64];
+  __shared__ float RED[NW * 64];
+  constexpr int NT = 64 * NW;
+  const int lane = threadIdx.x & 63;
+  const int w = uniform_i(threadIdx.x >> 6);
+  const int e = blockIdx.x;
+  const int N = a.N;
+  const int rows_pad = (N + 15) & ~15;
+  const int ntiles = rows_pad >> 4;
+  const size_t R0 = (size_t)e * N;
+  const size_t RT = (size_t)a.B * N;
+  float* G = gbuf + (size_t)e * rows_pad * 64;  // gathered-gradient source rows
+  const float* P = a.P;
+  const float* sv = a.sv;
+  float* gr = a.gr;
+  const int s4 = lane >> 4;
+  const int c16 = lane & 15;
+  const int gid = a.gids[e];
+  const uint32_t* __restrict__ eg = a.gs.edges + a.gs.edge_base[gid];
+  const double* __restrict__ ewg = a.gs.edge_weights + a.gs.edge_base[gid];  // FW only
+  auto rinfo = [&](int r) { return row_info_packed(pack_row_info(a, e, r, N)); };
+  auto SV = [&](int t) { return sv + (size_t)t * RT * 64; };
+  auto GR = [&](int t) { return gr + (size_t)t * RT * 64; };
+  const float* MEAN = sv + (size_t)SV_NODE_TENSORS * RT * 64;
+  const float* PP = MEAN + (size_t)a.B * 64;
+  float* DP = gr + (size_t)GR_NODE_TENSORS * RT * 64;
+  float* DWRA = DP + (size_t)a.B * 64;
+  float* DWRB = DWRA + (size_t)a.B * 64;
+  float* DBR = DWRB + (size_t)a.B * 64;
+  float* DWA = DBR + ((a.B + 63) & ~63);  // [B][64]
+  const bool xwide = a.xw == 16;
+
+  for (int r = threadIdx.x; r < rows_pad; r += NT) DQ[r] = r < N ? a.dq[R0 + r] : 0.f;
+  __syncthreads();
+
+  // ---- readout backward (mpnn.py:143-159): dWr[64:] = sum_v dq_v h3_v over all waves, the rest on wave 0 ----
+  {
+    const float* h3 = SV(SV_H3) + R0 * 64;
+    float dwb = 0.f;
+    for (int v = w; v < N; v += NW) {
+      const float dv = DQ[v];
+      if (dv != 0.f) dwb = fmaf(dv, h3[(size_t)v * 64 + lane], dwb);
+    }
+    RED[w * 64 + lane] = dwb;
+  }
+  __syncthreads();
+  if (w == 0) {
+    float s = 0.f;
+    for (int v = lane; v < N; v += 64) s += DQ[v];
+    const float S = wave_sum_f(s);
+    const float p = PP[(size_t)e * 64 + lane];
+    const float wr = P[PK_WR + lane];
+    const float dp = wr * S * (p > 0.f ? 1.f : 0.f);
+    DP[(size_t)e * 64 + lane] = dp;
+    DWRA[(size_t)e * 64 + lane] = relu(p) * S;
+    if (lane == 0) DBR[e] = S;
+    float dmean = 0.f;
+#pragma unroll 16
+    for (int k = 0; k < 64; ++k) dmean = fmaf(P[PK_WP + k * 64 + lane], __shfl(dp, k, 64), dmean);
+    DMEAN[lane] = dmean / (float)N;
+    float dwb = 0.f;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) dwb += RED[k * 64 + lane];  // fixed order
+    DWRB[(size_t)e * 64 + lane] = dwb;
+  }
+  __syncthreads();
+
+  // dh3 (A layout): dq_i * wr[64+f] + dmean_f / N  -> GR_DH rows
+  for (int t = w; t < ntiles; t += NW) {
+    const int r = t * 16 + c16;
+    if (r < N) {
+      const float dqi = DQ[r];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int f = 16 * c + 4 * s4;
+        const float4 dm = f4(DMEAN + f);
+        st4(GR(GR_DH) + (R0 + r) * 64 + f,
+            make_float4(fmaf(dqi, P[PK_WR + 64 + f + 0], dm.x), fmaf(dqi, P[PK_WR + 64 + f + 1], dm.y),
+                        fmaf(dqi, P[PK_WR + 64 + f + 2], dm.z), fmaf(dqi, P[PK_WR + 64 + f + 3], dm.w)));
+      }
+    }
+  }
+
+  // ---- update layers in reverse (mpnn.py:114-120) ----
+  const uint16_t* BFP = reinterpret_cast<const uint16_t*>(P + PK_BF);
+  for (int layer = 2; layer >= 0; --layer) {
+    const uint16_t* BFT = BFP + BFT_LAYER + layer * BF_LAYER_STRIDE;  // Wm^T halves, then Wu^T halves
+    for (int t = w; t < ntiles; t += NW) {
+      const int r = t * 16 + c16;
+      const bool valid = r < N;
+      const size_t ro = (R0 + r) * 64 + 4 * s4;
+      // duu = dh' * [h' > 0]
+      float4 duu[4], mv[4];
+      const float* hnext = SV(SV_H0 + layer + 1) + ro;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float4 hv = valid ? f4(hnext + 16 * c) : zero4();
+        const float4 dhv = valid ? f4(GR(GR_DH) + ro + 16 * c) : zero4();
+        mv[c] = valid ? f4(SV(SV_M0 + layer) + ro + 16 * c) : zero4();
+        duu[c] = make_float4(hv.x > 0.f ? dhv.x : 0.f, hv.y > 0.f ? dhv.y : 0.f, hv.z > 0.f ? dhv.z : 0.f,
+                             hv.w > 0.f ? dhv.w : 0.f);
+        if (valid) st4(GR(GR_DUU0 + layer) + ro + 16 * c, duu[c]);
+      }
+      // [dh_direct, dm] = duu . Wu
+      f32x4 d8[8];
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt) d8[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      bf3_t2(d8, duu, BFT + 2 * BF_HALF, lane);
+      // dum = dm * [m > 0]
+      float4 dum[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        dum[c] = make_float4(mv[c].x > 0.f ? d8[4 + c][0] : 0.f, mv[c].y > 0.f ? d8[4 + c][1] : 0.f,
+                             mv[c].z > 0.f ? d8[4 + c][2] : 0.f, mv[c].w > 0.f ? d8[4 + c][3] : 0.f);
+        if (valid) {
+          st4(GR(GR_DUM0 + layer) + ro + 16 * c, dum[c]);
+          st4(GR(GR_DH) + ro + 16 * c, make_float4(d8[c][0], d8[c][1], d8[c][2], d8[c][3]));
+        }
+      }
+      // [dagg, de] = dum . Wm;  G rows <- dagg / norm  (d(agg)/d(A.h) = 1/norm)
+#pragma unroll
+      for (int nt = 0; nt < 8; ++nt) d8[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      bf3_t2(d8, dum, BFT, lane);
+      const float nf = (float)rinfo(r).norm;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        st4(G + (size_t)r * 64 + 16 * c + 4 * s4,
+            valid ? make_float4(d8[c][0] / nf, d8[c][1] / nf, d8[c][2] / nf, d8[c][3] / nf) : zero4());
+        if (valid) {
+          float* de = GR(GR_DE) + ro + 16 * c;
+          const float4 prev = layer == 2 ? zero4() : f4(de);
+          st4(de, make_float4(prev.x + d8[4 + c][0], prev.y + d8[4 + c][1], prev.z + d8[4 + c][2],
+                              prev.w + d8[4 + c][3]));
+        }
+      }
+    }
+    __threadfence();  // release the G rows and invalidate this CU's L1 before other waves gather them
+    __syncthreads();
+    // dh_l = dh_direct + A^T . (dagg / norm)   (A symmetric: a gather over the node's own row)
+    for (int t = w; t < ntiles; t += NW) {
+      const int r = t * 16 + c16;
+      if (r < N) {
+        const RowInfo ri = rinfo(r);
+        float* dhp = GR(GR_DH) + (R0 + r) * 64 + 4 * s4;
+        float4 acc[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[c] = f4(dhp + 16 * c);
+        for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+          const float wv = edge_wf<FW>(ex, ewg, q);
+          const float* gv = G + (size_t)edge_col(ex) * 64 + 4 * s4;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float4 hv = f4(gv + 16 * c);
+            acc[c].x = fmaf(wv, hv.x, acc[c].x);
+            acc[c].y = fmaf(wv, hv.y, acc[c].y);
+            acc[c].z = fmaf(wv, hv.z, acc[c].z);
+            acc[c].w = fmaf(wv, hv.w, acc[c].w);
+          }
+        });
+#pragma unroll
+        for (int c = 0; c < 4; ++c) st4(dhp + 16 * c, acc[c]);
+      }
+    }
+    __syncthreads();  // every wave done gathering before the next phase rewrites G
+  }
+
+  // ---- h0 = relu(W0.x): du0;  edge embedding (mpnn.py:89-104): due, G rows <- dEagg / norm ----
+  for (int t = w; t < ntiles; t += NW) {
+    const int r = t * 16 + c16;
+    const bool valid = r < N;
+    float4 due[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const size_t off = (R0 + r) * 64 + 16 * c + 4 * s4;
+      if (valid) {
+        const float4 hv = f4(SV(SV_H0) + off);
+        const float4 dhv = f4(GR(GR_DH) + off);
+        st4(GR(GR_DU0) + off, make_float4(hv.x > 0.f ? dhv.x : 0.f, hv.y > 0.f ? dhv.y : 0.f,
+                                          hv.z > 0.f ? dhv.z : 0.f, hv.w > 0.f ? dhv.w : 0.f));
+      }
+      const float4 ev = valid ? f4(SV(SV_E) + off) : zero4();
+      const float4 dv = valid ? f4(GR(GR_DE) + off) : zero4();
+      due[c] = make_float4(ev.x > 0.f ? dv.x : 0.f, ev.y > 0.f ? dv.y : 0.f, ev.z > 0.f ? dv.z : 0.f,
+                           ev.w > 0.f ? dv.w : 0.f);
+      if (valid) st4(GR(GR_DUE) + off, due[c]);
+    }
+    f32x4 d4[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) d4[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    mm_bf3_lean(d4, due, BFP + BFT_WF, lane);
+    const float nf = (float)rinfo(r).norm;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      st4(G + (size_t)r * 64 + 16 * c + 4 * s4,
+          valid ? make_float4(d4[c][0] / nf, d4[c][1] / nf, d4[c][2] / nf, d4[c][3] / nf) : zero4());
+  }
+  __threadfence();
+  __syncthreads();
+  // dz_j = sum_{i in N(j)} G_i * [w_ij wa + z_j > 0];  dwa += same * w_ij
+  {
+    float wa[16];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) wa[4 * c + i] = P[PK_WA + 16 * c + 4 * s4 + i];
+    float dwa[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) dwa[i] = 0.f;
+    for (int t = w; t < ntiles; t += NW) {
+      const int r = t * 16 + c16;
+      const bool valid = r < N;
+      const RowInfo ri = rinfo(r);
+      // z = Wx.x of the lane's node for its 16 features (same expression as forward phase A)
+      float4 x0 = zero4(), x1 = zero4(), x2 = zero4(), x3 = zero4();
+      if (valid) {
+        const float* xr = a.x + (R0 + r) * a.xw;
+        x0 = f4(xr);
+        x1 = f4(xr + 4);
+        if (xwide) { x2 = f4(xr + 8); x3 = f4(xr + 12); }
+      }
+      float z[16], dz[16];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float* wx = P + PK_WX + (16 * c + 4 * s4 + i) * 8;
+          const float4 w0 = f4(wx), w1 = f4(wx + 4);
+          z[4 * c + i] = w0.x * x0.x + w0.y * x0.y + w0.z * x0.z + w0.w * x0.w + w1.x * x1.x + w1.y * x1.y +
+                         w1.z * x1.z + w1.w * x1.w;
+          if (xwide) {  // same left-to-right order as the forward's xdot_hi term
+            const float* wh = P + PK_WXH + (16 * c + 4 * s4 + i) * 8;
+            const float4 h0 = f4(wh), h1 = f4(wh + 4);
+            z[4 * c + i] += h0.x * x2.x + h0.y * x2.y + h0.z * x2.z + h0.w * x2.w + h1.x * x3.x + h1.y * x3.y +
+                            h1.z * x3.z + h1.w * x3.w;
+          }
+        }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dz[i] = 0.f;
+      for_edges(eg, ri.e0, ri.e1, [&](uint32_t ex, int q) {
+        const float wv = edge_wf<FW>(ex, ewg, q);
+        const float* gi = G + (size_t)edge_col(ex) * 64 + 4 * s4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float4 gv = f4(gi + 16 * c);
+          const float g4[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const int kk = 4 * c + i;
+            const float gm = fmaf(wv, wa[kk], z[kk]) > 0.f ? g4[i] : 0.f;
+            dz[kk] += gm;
+            dwa[kk] = fmaf(gm, wv, dwa[kk]);
+          }
+        }
+      });
+      if (valid) {
+        float* dzp = GR(GR_DZ) + (R0 + r) * 64 + 4 * s4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) st4(dzp + 16 * c, make_float4(dz[4 * c], dz[4 * c + 1], dz[4 * c + 2], dz[4 * c + 3]));
+      }
+    }
+    // reduce dwa over the 16 node lanes sharing s4, then over waves (fixed order)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float v = dwa[i];
+      v += __shfl_xor(v, 1, 64);
+      v += __shfl_xor(v, 2, 64);
+      v += __shfl_xor(v, 4, 64);
+      v += __shfl_xor(v, 8, 64);
+      dwa[i] = v;
+    }
+    if (c16 == 0) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) RED[w * 64 + 16 * c + 4 * s4 + i] = dwa[4 * c + i];
+    }
+    __syncthreads();
+    if (w == 0) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < NW; ++k) s += RED[k * 64 + lane];
+      DWA[(size_t)e * 64 + lane] = s;
+    }
   }
 }
 
@@ -1420,6 +1757,56 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
     case ECO_ROUTE_CSR: return launch_csr(a, true, false, st);
     default: return fail(ECO_ERR_ARG, "MPNN backward supports N <= 512");
   }
+}
+
+// eco_mpnn_grad_large's workspace: a 256 B header (the call's max degree), the SV_* node tensors + MEAN + P, the GR_*
+// tensors + per-graph partials (mpnn_grad_ws_bytes), one [rows_pad][64] gather-source buffer per episode, the
+// forward's three ping-pong row buffers, the weight-gradient slabs; every part 256 B aligned.  total = 0: no such
+// call (N outside (512, 2048], batch < 1 or batch * n_spins rows beyond the 32-bit row index of the weight gradients).
+GradLargeLayout eco::mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
+  GradLargeLayout L{};
+  if (n_spins <= MPNN_MAX_SPINS || n_spins > MPNN_MAX_SPINS_LARGE || batch < 1) return L;
+  const size_t RT = (size_t)n_spins * batch;
+  if (RT > (size_t)INT32_MAX / 64) return L;
+  const size_t rows_pad = ((size_t)n_spins + 15) & ~(size_t)15;
+  L.sv = 256;
+  L.gr = L.sv + align_up(sv_mask_offset_floats(RT, batch) * sizeof(float), 256);
+  L.g = L.gr + align_up(mpnn_grad_ws_bytes(n_spins, batch), 256);
+  L.hbuf = L.g + (size_t)batch * rows_pad * 64 * sizeof(float);
+  L.slabs = L.hbuf + (size_t)batch * rows_pad * 64 * 3 * sizeof(float);
+  L.total = L.slabs + slab_bytes;
+  return L;
+}
+
+// The launches of eco_mpnn_grad_large before the weight-gradient tail: the call's max degree, the saving forward,
+// the backward over global rows.  8 waves, {float weights} x {8-, 16-float rows} forwards, {float weights} backwards.
+int eco::mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                                const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
+                                void* workspace, const GradLargeLayout& L, hipStream_t st) {
+  MpnnArgs a;
+  if (const int rc = prepare(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, ECO_NORM_PER_CALL)) return rc;
+  if (!L.total || a.gpb != 1) return fail(ECO_ERR_ARG, "eco_mpnn_grad_large supports 512 < N <= 2048");
+  char* ws = (char*)workspace;
+  a.call_maxdeg = (int*)ws;
+  a.sv = (float*)(ws + L.sv);
+  a.gr = (float*)(ws + L.gr);
+  a.dq = dq;
+  float* gbuf = (float*)(ws + L.g);
+  float* hbuf = (float*)(ws + L.hbuf);
+  call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)ws);
+  const int rows_pad = (a.N + 15) & ~15;
+  const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
+  const bool wide = a.xw == 16, fw = a.gs.edge_weights != nullptr;
+  if (fw) {
+    if (wide) launch_lds(mpnn_forward_large_kernel<8, true, 16, true>, a.B, 512, lds, st, a, hbuf);
+    else launch_lds(mpnn_forward_large_kernel<8, true, 8, true>, a.B, 512, lds, st, a, hbuf);
+    mpnn_backward_large_kernel<8, true><<<a.B, 512, 0, st>>>(a, gbuf);
+  } else {
+    if (wide) launch_lds(mpnn_forward_large_kernel<8, false, 16, true>, a.B, 512, lds, st, a, hbuf);
+    else launch_lds(mpnn_forward_large_kernel<8, false, 8, true>, a.B, 512, lds, st, a, hbuf);
+    mpnn_backward_large_kernel<8, false><<<a.B, 512, 0, st>>>(a, gbuf);
+  }
+  return check_launch("mpnn_grad_large");
 }
 
 // ---- split2_pk hazard probe (the v_fma_mix inline asm carries its own wait states) ----

@@ -690,18 +690,13 @@ extern "C" size_t eco_mpnn_backward_workspace_bytes(int32_t n_spins, int32_t bat
   return align_up(g, 256) + slab_bytes();
 }
 
-extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
-                                 const int32_t* graph_ids, int32_t batch, const float* obs_x, const void* saved,
-                                 const float* dq, float* grad, void* workspace, eco_stream_t stream) {
-  if (!grad || !workspace) return fail(ECO_ERR_ARG, "null grad/workspace");
-  hipStream_t st = (hipStream_t)stream;
-  int rc = mpnn_backward_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, saved, dq, workspace, st);
-  if (rc) return rc;
-  const int N = gs->n_spins;
+// The weight-gradient tail shared by eco_mpnn_backward and eco_mpnn_grad_large: dW = sum_nodes dY^T X for every Linear
+// from the saved activations `sv` and the activation gradients `gr` (both [tensor][R][64] then per graph, R = batch * N
+// rows), split-K into `slabs` and reduced in a fixed order into grad; then the column sums of the per-graph /
+// per-block partials (nblk rows of DWA).
+static int wgrad_tail(const float* sv, const float* gr, int32_t n_obs_in, int N, int32_t batch, int nblk,
+                      const float* obs_x, float* slabs, float* grad, hipStream_t st) {
   const size_t RT = (size_t)batch * N;
-  if (RT > (size_t)INT32_MAX / 64) return fail(ECO_ERR_ARG, "batch * n_spins too large");
-  const float* sv = (const float*)saved;
-  const float* gr = (const float*)workspace;
   auto SV = [&](int t) { return sv + (size_t)t * RT * 64; };
   auto GR = [&](int t) { return gr + (size_t)t * RT * 64; };
   const float* MEAN = sv + (size_t)SV_NODE_TENSORS * RT * 64;
@@ -710,9 +705,6 @@ extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const ec
   const float* DWRB = DWRA + (size_t)batch * 64;
   const float* DBR = DWRB + (size_t)batch * 64;
   const float* DWA = DBR + (((size_t)batch + 63) & ~63ull);
-  const int gpb = graphs_per_block(N, batch);
-  const int nblk = (batch + gpb - 1) / gpb;
-  float* slabs = (float*)((char*)workspace + align_up(mpnn_grad_ws_bytes(N, batch), 256));
   const FlatOffsets fo = flat_offsets(n_obs_in);
   WJobs J{};
   int n = 0;
@@ -759,6 +751,44 @@ extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const ec
   for (int k = 0; k < 4; ++k) CJ.first[k + 1] = CJ.first[k] + CJ.j[k].C;
   colsum_jobs_kernel<<<CJ.first[4], 256, 0, st>>>(CJ);
   return check_launch("mpnn_backward_wgrad");
+}
+
+extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                                 const int32_t* graph_ids, int32_t batch, const float* obs_x, const void* saved,
+                                 const float* dq, float* grad, void* workspace, eco_stream_t stream) {
+  if (!grad || !workspace) return fail(ECO_ERR_ARG, "null grad/workspace");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = mpnn_backward_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, saved, dq, workspace, st);
+  if (rc) return rc;
+  const int N = gs->n_spins;
+  if ((size_t)batch * N > (size_t)INT32_MAX / 64) return fail(ECO_ERR_ARG, "batch * n_spins too large");
+  const int gpb = graphs_per_block(N, batch);
+  float* slabs = (float*)((char*)workspace + align_up(mpnn_grad_ws_bytes(N, batch), 256));
+  return wgrad_tail((const float*)saved, (const float*)workspace, n_obs_in, N, batch, (batch + gpb - 1) / gpb, obs_x,
+                    slabs, grad, st);
+}
+
+extern "C" size_t eco_mpnn_grad_large_workspace_bytes(int32_t n_spins, int32_t batch) {
+  return mpnn_grad_large_layout(n_spins, batch, slab_bytes()).total;
+}
+
+extern "C" int eco_mpnn_grad_large(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                                   const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
+                                   float* grad, void* workspace, eco_stream_t stream) {
+  if (!packed || !gs || !graph_ids || !obs_x || !dq || !grad || !workspace)
+    return fail(ECO_ERR_ARG, "eco_mpnn_grad_large: null argument");
+  if (batch < 1) return fail(ECO_ERR_ARG, "batch must be >= 1");
+  const int N = gs->n_spins;
+  if (N <= MPNN_MAX_SPINS || N > MPNN_MAX_SPINS_LARGE)
+    return fail(ECO_ERR_ARG, "eco_mpnn_grad_large supports 512 < N <= 2048 (eco_mpnn_backward below)");
+  const GradLargeLayout L = mpnn_grad_large_layout(N, batch, slab_bytes());
+  if (!L.total) return fail(ECO_ERR_ARG, "batch * n_spins too large");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = mpnn_grad_large_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, workspace, L, st))
+    return rc;
+  char* ws = (char*)workspace;
+  return wgrad_tail((const float*)(ws + L.sv), (const float*)(ws + L.gr), n_obs_in, N, batch, batch, obs_x,
+                    (float*)(ws + L.slabs), grad, st);
 }
 
 extern "C" int eco_dqn_td_loss(const float* q_s, const float* q_target_next, const int32_t* a_star,

@@ -9,7 +9,8 @@ advances B episodes.  Everything on the step path runs in libecohip:
   replay    -> device ring push / distinct-index sample (dqn/utils.py:28-83)
   train     -> online(s') argmax, target(s') gather, online(s) forward with saved
                activations, TD + MSE / Huber gradient, MPNN backward, optional gradient-norm clipping,
-               Adam (dqn.py:403-451)
+               Adam (dqn.py:403-451); above 512 vertices online(s) is an inference forward and the
+               gradient one self-contained call that recomputes it (MPNN.grad_large)
 Schedules are per env-step as in the reference; a vector step advances the
 counter by B.  The replay ratio of the reference (minibatch_size/update_frequency
 samples per env-step, 64/32 = 2 in train_eco.py:136-137) is kept by running
@@ -214,9 +215,16 @@ class DQN:
         self.dq = torch.empty(m, self.N, device=dev)
         self.sqerr = torch.empty(m, device=dev)
         self.loss_dev = torch.zeros(1, device=dev)
-        self.saved = torch.empty(self.network.saved_bytes(self.N, m), dtype=torch.uint8, device=dev)
-        self.bw_ws = torch.empty(_lib.lib.eco_mpnn_backward_workspace_bytes(self.N, m), dtype=torch.uint8,
-                                 device=dev)
+        # above 512 vertices the gradient is one self-contained call (MPNN.grad_large) with one workspace; there is
+        # no saved-activation buffer between a forward and a backward
+        self._large = self.N > _lib.MPNN_MAX_SPINS
+        if self._large:
+            self.saved = self.bw_ws = None
+            self.grad_ws = torch.empty(self.network.grad_large_bytes(self.N, m), dtype=torch.uint8, device=dev)
+        else:
+            self.saved = torch.empty(self.network.saved_bytes(self.N, m), dtype=torch.uint8, device=dev)
+            self.bw_ws = torch.empty(_lib.lib.eco_mpnn_backward_workspace_bytes(self.N, m), dtype=torch.uint8,
+                                     device=dev)
         self._train_m = m
         self._actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._obs = [self.env.obs_x, torch.zeros_like(self.env.obs_x)]
@@ -296,7 +304,10 @@ class DQN:
                                             ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
                                             self._loss_kind, _lib.ptr(self.dq), _lib.ptr(self.sqerr),
                                             _lib.ptr(loss_dev), _lib.stream_ptr()))
-        net.backward_graphs(xs, self.graphs, gid, self.saved, self.dq, self.grad, workspace=self.bw_ws)
+        if self._large:
+            net.grad_large(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
+        else:
+            net.backward_graphs(xs, self.graphs, gid, self.saved, self.dq, self.grad, workspace=self.bw_ws)
         # RCCL sum over xGMI (233.7 KB) on the collective's stream, the mean folded into Adam; independent work
         # (the caller's `overlap`) is issued on this stream meanwhile
         work, scale = allreduce_gradients_async(self.grad)

@@ -359,6 +359,22 @@ int eco_mpnn_backward(const float *packed, int32_t n_obs_in, const eco_graph_set
                       int32_t batch, const float *obs_x, const void *saved, const float *dq, float *grad,
                       void *workspace, eco_stream_t stream);
 
+/* Training above 512 vertices (dqn.py:440-449 has no size limit): the gradient of 512 < N <= 2048 graphs in ONE
+ * self-contained call.  grad[flat, state_dict order] = d(sum dq . Q)/dparams, Q being the network's output on obs_x
+ * with norm scope ECO_NORM_PER_CALL (the training scope).  The call recomputes the forward on per-episode
+ * global-memory rows inside itself, so no `saved` buffer crosses the ABI: Q(s) for the TD error comes from an
+ * ordinary eco_mpnn_forward (saved = NULL).  +-1, integer and float (gs->edge_weights) weights; 8- and 16-float
+ * observation rows.  grad is overwritten; no atomics, every reduction in a fixed order: bitwise reproducible.
+ * workspace: eco_mpnn_grad_large_workspace_bytes(n_spins, batch) bytes, all scratch -- a 256 B header with the
+ * call's max degree, the saved node tensors + MEAN + P, the activation gradients and per-graph partials, one
+ * [rows_pad][64] gather-source buffer per episode, the forward's three row buffers, the weight-gradient slabs.
+ * ECO_ERR_ARG before any launch for N <= 512 (eco_mpnn_backward's range) or N > 2048, a NULL pointer, batch < 1,
+ * batch * n_spins > INT32_MAX / 64 and whatever eco_mpnn_forward rejects; the bytes query returns 0 for such sizes. */
+size_t eco_mpnn_grad_large_workspace_bytes(int32_t n_spins, int32_t batch);
+int eco_mpnn_grad_large(const float *packed, int32_t n_obs_in, const eco_graph_set *gs, const int32_t *graph_ids,
+                        int32_t batch, const float *obs_x, const float *dq, float *grad, void *workspace,
+                        eco_stream_t stream);
+
 /* Double-DQN TD target and MSE gradient (dqn.py:409-440, reversible env):
  * q_t = q_target_next[b][a_star[b]] (a_star = argmax of the online net on s'),
  * td = r + (1 - done) * gamma * q_t; loss = mean((q_s[b][a_b] - td)^2);
