@@ -10,6 +10,10 @@
 // BA: preferential attachment exactly as networkx.barabasi_albert_graph (initial star of m
 //     targets, repeated-nodes list, m distinct draws per new vertex); the process is
 //     sequential per graph, so one wave owns one graph with its lists in LDS.
+// REGULAR: d-regular by the pairing algorithm of networkx.random_regular_graph (RandomRegularGraphGenerator,
+//     utils.py:238-275); sequential per graph with restarts, one wave per graph as BA (regular_kernel).
+// WS: the ring lattice of networkx.watts_strogatz_graph(n, k, 0) (RandomWattsStrogatzGraphGenerator,
+//     utils.py:277-314, which always passes p = 0); wave per row, no RNG.  Rewiring (p > 0) is not implemented.
 // Weights: +-1 fair per edge (EdgeType.DISCRETE, symmetric hash), 1 (UNIFORM), or float64 uniform in (-1, 1)
 // (EdgeType.RANDOM): w = 2u - 1, u the top 53 bits of the same symmetric hash, written to gs.edge_weights with
 // sign(w) in the packed word.
@@ -213,6 +217,166 @@ __global__ void ba_kernel(int first, int count, int N, int m, uint64_t seed, int
   }
 }
 
+// Random d-regular graph (networkx.random_regular_graph: the pairing algorithm of Steger and Wormald), one wave
+// per graph.  LDS per wave: stub list [N d], adjacency lists [N][d], degree [N], potential count [N], one word; int32.
+// An attempt starts from the stub list (every vertex d times) and runs rounds: shuffle the stubs (Fisher-Yates),
+// pair consecutive stubs, accept a pair that is neither a loop nor an edge already (edges of this round
+// included), count the stubs of a rejected pair as potential.  No potential stubs: done.  No two distinct
+// potential vertices that are not joined yet: the attempt failed and restarts from scratch.  Otherwise the stub
+// list is rebuilt from the potential counts (in vertex order; the shuffle makes the order irrelevant).
+// Lane 0 shuffles and pairs, as the definition is sequential in both; the wave fills and rebuilds the lists,
+// tests the potential vertices, sorts the rows and writes them out.
+// Termination: a round that adds an edge can happen N d / 2 times in an attempt; a round that adds none (every
+// pair of a short stub list rejected although a joinable pair remains, e.g. a a b b shuffled to (a a)(b b)) is a
+// stall, and an attempt with more than kRegularMaxStalls of them counts as failed; so an attempt has at most
+// N d / 2 + kRegularMaxStalls + 1 rounds, and there are at most ECO_REGULAR_MAX_RESTARTS + 1 attempts.  Then the
+// graph is left empty (valid = 0 after prepare) and ECO_ERR_GRAPH goes into the error word.
+constexpr int kRegularMaxStalls = 64;
+
+// uniform integer in [0, range) from a 64-bit draw (multiply-high; bias below range * 2^-64)
+__device__ __forceinline__ int draw_below(uint64_t r, int range) { return (int)__umul64hi(r, (uint64_t)range); }
+
+__global__ void regular_kernel(int first, int count, int N, int d, uint64_t seed, int kind, int32_t* row_ptr,
+                               const int64_t* edge_base, uint32_t* edges, double* weights, int32_t* err) {
+  extern __shared__ int32_t sm[];
+  const int lane = threadIdx.x;
+  const int gi = blockIdx.x;
+  if (gi >= count) return;
+  const int g = first + gi;
+  const int S = N * d;
+  int32_t* stubs = sm;        // [S]
+  int32_t* adj = stubs + S;   // [N][d]
+  int32_t* deg = adj + S;     // [N]
+  int32_t* pot = deg + N;     // [N]
+  int32_t& sh_added = pot[N]; // edges added by the round, lane 0 to the wave
+  uint64_t ctr = 0;           // draw counter (used by lane 0 only)
+  bool done = false;
+  for (int attempt = 0; attempt <= ECO_REGULAR_MAX_RESTARTS && !done; ++attempt) {
+    for (int i = lane; i < N; i += 64) deg[i] = 0;
+    for (int s = lane; s < S; s += 64) stubs[s] = s % N;
+    int ns = S, stalls = 0;  // wave-uniform
+    __syncthreads();
+    while (true) {  // one round per iteration: it adds an edge, or stalls, or ends the attempt
+      if (ns == 0) {
+        done = true;
+        break;
+      }
+      for (int i = lane; i < N; i += 64) pot[i] = 0;
+      __syncthreads();
+      if (lane == 0) {
+        for (int i = ns - 1; i > 0; --i) {
+          const int j = draw_below(rng3(seed, (uint64_t)g, ctr++), i + 1);
+          const int32_t t = stubs[i];
+          stubs[i] = stubs[j];
+          stubs[j] = t;
+        }
+        int added = 0;
+        for (int p = 0; p < ns; p += 2) {
+          const int a = stubs[p], b = stubs[p + 1];
+          bool reject = a == b;
+          for (int q = 0; q < deg[a] && !reject; ++q) reject = adj[a * d + q] == b;
+          if (reject) {
+            ++pot[a];
+            ++pot[b];
+          } else {  // deg <= d: every edge at a vertex consumed one of its d stubs
+            adj[a * d + deg[a]++] = b;
+            adj[b * d + deg[b]++] = a;
+            ++added;
+          }
+        }
+        sh_added = added;
+      }
+      __syncthreads();
+      // potential vertices P; u can still be joined iff fewer than P - 1 of its neighbours are potential
+      int np = 0;
+      for (int i0 = 0; i0 < N; i0 += 64) np += __popcll(__ballot(i0 + lane < N && pot[i0 + lane] > 0));
+      if (np == 0) {
+        done = true;
+        break;
+      }
+      bool open = false;
+      for (int u = lane; u < N; u += 64) {
+        if (pot[u] == 0) continue;
+        int joined = 0;
+        for (int q = 0; q < deg[u]; ++q) joined += pot[adj[u * d + q]] > 0;
+        open = open || joined < np - 1;
+      }
+      const bool suitable = __ballot(open) != 0;
+      if (uniform_i(sh_added) == 0) ++stalls;
+      if (!suitable || stalls > kRegularMaxStalls) break;  // failed attempt
+      // stub list of the next round: vertex i repeated pot[i] times (wave scan over the vertices)
+      int base = 0;
+      for (int i0 = 0; i0 < N; i0 += 64) {
+        const int i = i0 + lane;
+        const int c = i < N ? pot[i] : 0;
+        int v = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int u = __shfl_up(v, o, 64);
+          if (lane >= o) v += u;
+        }
+        for (int q = 0; q < c; ++q) stubs[base + v - c + q] = i;  // total = 2 x rejected pairs <= ns
+        base += __shfl(v, 63, 64);
+      }
+      ns = base;
+      __syncthreads();
+    }
+    __syncthreads();
+  }
+  int32_t* rp = row_ptr + (size_t)g * (N + 1);
+  if (!done) {  // restarts exhausted: an empty graph (valid = 0 after prepare)
+    for (int i = lane; i <= N; i += 64) rp[i] = 0;
+    if (lane == 0) atomicCAS(err, 0, ECO_ERR_GRAPH);
+    return;
+  }
+  for (int i = lane; i <= N; i += 64) rp[i] = i * d;
+  uint32_t* ed = edges + edge_base[g];
+  double* ew = weights ? weights + edge_base[g] : nullptr;
+  for (int i = lane; i < N; i += 64) {  // every row has d entries: sort by column, then store
+    int32_t* row = adj + i * d;
+    for (int q = 1; q < d; ++q) {
+      const int32_t x = row[q];
+      int r = q - 1;
+      while (r >= 0 && row[r] > x) {
+        row[r + 1] = row[r];
+        --r;
+      }
+      row[r + 1] = x;
+    }
+    for (int q = 0; q < d; ++q) store_edge(ed, ew, (long long)i * d + q, row[q], seed, g, i, row[q], N, kind);
+  }
+}
+
+// Ring lattice (networkx.watts_strogatz_graph(N, k, 0)): i ~ j iff 1 <= min(|i - j|, N - |i - j|) <= h, h = k / 2.
+// No RNG in the structure; wave per row, ballot fill as er_fill_kernel, every row has rdeg = min(2 h, N - 1) entries.
+__global__ void ws_kernel(int first, int count, int N, int h, int rdeg, uint64_t seed, int kind, int32_t* row_ptr,
+                          const int64_t* edge_base, uint32_t* edges, double* weights) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= (long long)count * N) return;
+  const int g = first + (int)(row / N);
+  const int i = (int)(row % N);
+  int32_t* rp = row_ptr + (size_t)g * (N + 1);
+  if (lane == 0) {
+    if (i == 0) rp[0] = 0;
+    rp[i + 1] = (i + 1) * rdeg;
+  }
+  uint32_t* ed = edges + edge_base[g];
+  double* ew = weights ? weights + edge_base[g] : nullptr;
+  int pos = i * rdeg;
+  for (int j0 = 0; j0 < N; j0 += 64) {
+    const int j = j0 + lane;
+    const int dist = j > i ? j - i : i - j;
+    const bool on = j < N && j != i && min(dist, N - dist) <= h;
+    const uint64_t bal = __ballot(on);
+    if (on) {
+      const int k = __popcll(bal & ((1ull << lane) - 1ull));
+      store_edge(ed, ew, pos + k, j, seed, g, i, j, N, kind);
+    }
+    pos += __popcll(bal);
+  }
+}
+
 }  // namespace eco
 
 using namespace eco;
@@ -256,6 +420,27 @@ extern "C" int eco_graphs_generate(eco_graph_set* gs, int32_t first, int32_t cou
     (void)hipFuncSetAttribute((const void*)ba_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     ba_kernel<<<count, 64, lds, st>>>(first, count, N, m, seed, weight_kind, rp, gs->edge_base, ed, ewt, edge_cap,
                                       err);
+  } else if (kind == ECO_GRAPH_REGULAR) {
+    if (!(param >= 0.0 && param < (double)N) || param != (double)(int)param)
+      return fail(ECO_ERR_ARG, "regular-graph degree d must be an integer in [0, N)");
+    const int d = (int)param;
+    const long long S = (long long)N * d;
+    if (S & 1) return fail(ECO_ERR_ARG, "no d-regular graph on N vertices: N d must be even");
+    const size_t lds = (2 * (size_t)S + 2 * (size_t)N + 1) * sizeof(int32_t);
+    if (lds > 160 * 1024) return fail(ECO_ERR_ARG, "regular graph too large for one workgroup's LDS");
+    if (edge_cap < S) return fail(ECO_ERR_ARG, "edge slot smaller than the N d entries of a d-regular graph");
+    (void)hipFuncSetAttribute((const void*)regular_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    regular_kernel<<<count, 64, lds, st>>>(first, count, N, d, seed, weight_kind, rp, gs->edge_base, ed, ewt, err);
+  } else if (kind == ECO_GRAPH_WS) {
+    if (!(param >= 0.0 && param <= (double)N) || param != (double)(int)param)
+      return fail(ECO_ERR_ARG, "ring-lattice k must be an integer in [0, N]");
+    const int h = (int)param / 2;
+    const int rdeg = 2 * h < N - 1 ? 2 * h : N - 1;  // h = N / 2 (N even): the antipode is one neighbour
+    if (edge_cap < (long long)N * rdeg)
+      return fail(ECO_ERR_ARG, "edge slot smaller than the N min(2 (k / 2), N - 1) entries of the ring lattice");
+    const long long rows = (long long)count * N;
+    ws_kernel<<<(int)((rows + 3) / 4), 256, 0, st>>>(first, count, N, h, rdeg, seed, weight_kind, rp, gs->edge_base,
+                                                     ed, ewt);
   } else {
     return fail(ECO_ERR_ARG, "unknown graph kind");
   }

@@ -32,7 +32,8 @@ ECO_MAX_SPINS = 2048
 MPNN_MAX_SPINS = 512          # saved-activation training (eco_mpnn_backward) up to here; eco_mpnn_grad_large above
 ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS)
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
-ECO_GRAPH_ER, ECO_GRAPH_BA = 1, 2
+ECO_GRAPH_ER, ECO_GRAPH_BA, ECO_GRAPH_REGULAR, ECO_GRAPH_WS = 1, 2, 3, 4
+ECO_REGULAR_MAX_RESTARTS = 256   # restarts of the pairing algorithm per regular graph before ECO_ERR_GRAPH
 ECO_WEIGHTS_UNIFORM, ECO_WEIGHTS_DISCRETE, ECO_WEIGHTS_RANDOM = 0, 1, 2   # eco_graphs_generate weight kinds
 ECO_LOSS_MSE, ECO_LOSS_HUBER = 0, 1   # eco_dqn_td_loss loss kinds
 # kernel-path policy bits (eco_set_kernel_paths)

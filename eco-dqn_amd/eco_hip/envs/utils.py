@@ -13,6 +13,8 @@ from enum import Enum
 
 import numpy as np
 
+from ..graphs import _integer_param, _regular_edges, _ring_edges
+
 
 class Stopping(Enum):
     NORMAL = 1
@@ -185,6 +187,49 @@ class RandomBarabasiAlbertGraphGenerator(GraphGenerator):
         return _symmetric(n, iu, ju, _edge_weights(self.edge_type, iu.size))
 
 
+def _mean_std(value, name):
+    if type(value) not in [list, tuple]:
+        value = [value, 0]
+    assert len(value) == 2, f"{name} must have length 2"
+    return value
+
+
+class RandomRegularGraphGenerator(GraphGenerator):
+    """Random d-regular graph with d = clip(int(normal(*d_node)), 0, n) per get() (src/envs/utils.py:238-275),
+    drawn by the pairing algorithm of networkx.random_regular_graph (graphs._regular_edges) on numpy's global
+    stream.  As there, a degree with n d odd or d >= n raises (ValueError here)."""
+
+    def __init__(self, n_spins=20, d_node=[2, 0], edge_type=EdgeType.DISCRETE, biased=False):
+        if biased:
+            raise NotImplementedError("biased graphs are not on the MaxCut hot path")
+        super().__init__(n_spins, edge_type, False)
+        self.d_node = _mean_std(d_node, "d_node")
+
+    def get(self, with_padding=False):
+        n = self.n_spins
+        d = int(np.clip(int(np.random.normal(*self.d_node)), 0, n))
+        iu, ju = _regular_edges(n, _integer_param("REG", n, d), np.random)
+        return _symmetric(n, iu, ju, _edge_weights(self.edge_type, iu.size))
+
+
+class RandomWattsStrogatzGraphGenerator(GraphGenerator):
+    """Ring lattice with k = clip(int(normal(*k_neighbours)), 0, n) per get(): every vertex joined to its k // 2
+    nearest neighbours on each side (src/envs/utils.py:277-314, which calls watts_strogatz_graph with a rewiring
+    probability of 0, so nothing is rewired)."""
+
+    def __init__(self, n_spins=20, k_neighbours=[2, 0], edge_type=EdgeType.DISCRETE, biased=False):
+        if biased:
+            raise NotImplementedError("biased graphs are not on the MaxCut hot path")
+        super().__init__(n_spins, edge_type, False)
+        self.k_neighbours = _mean_std(k_neighbours, "k_neighbours")
+
+    def get(self, with_padding=False):
+        n = self.n_spins
+        k = int(np.clip(int(np.random.normal(*self.k_neighbours)), 0, n))
+        iu, ju = _ring_edges(n, k)
+        return _symmetric(n, iu, ju, _edge_weights(self.edge_type, iu.size))
+
+
 def _edge_type_of(matrices):
     """EdgeType of a collection of adjacency matrices, from the set of weights they use: {0, 1} -> UNIFORM,
     {0, +-1} -> DISCRETE, anything else -> RANDOM (the classification the reference's known-graph generators
@@ -239,3 +284,33 @@ class SingleGraphGenerator(SetGraphGenerator):
         if bias is not None:
             self.biased = True
             self.graphs = [(matrix, bias)]
+
+
+class PerturbedGraphGenerator(GraphGenerator):
+    """Known graphs of one size plus symmetric Gaussian noise normal(perturb_mean, perturb_std) on their edges only
+    (src/envs/utils.py:385-436); EdgeType.RANDOM, so the graphs run on the float-weight path.  The known graph is
+    chosen as SetGraphGenerator chooses it; the lower triangle of one [N, N] normal draw is the noise."""
+
+    def __init__(self, matrices, perturb_mean=0, perturb_std=0.01, biases=None, ordered=False):
+        matrices = [np.asarray(m) for m in matrices]
+        if len({m.shape[0] for m in matrices}) != 1:
+            raise NotImplementedError("All graphs passed to PerturbedGraphGenerator must have the same dimension.")
+        if biases is not None:
+            raise NotImplementedError("Not implemented PerturbedGraphGenerator for biased graphs yet.")
+        super().__init__(matrices[0].shape[0], EdgeType.RANDOM, False)
+        self.perturb_mean = perturb_mean
+        self.perturb_std = perturb_std
+        self.graphs = matrices
+        self.ordered = ordered
+        self.i = 0
+
+    def get(self, with_padding=False):
+        if self.ordered:
+            m = self.graphs[self.i]
+            self.i = (self.i + 1) % len(self.graphs)
+        else:
+            m = self.graphs[random.sample(range(len(self.graphs)), 1)[0]]
+        noise = np.random.normal(self.perturb_mean, self.perturb_std, size=m.shape)
+        noise[m == 0] = 0
+        noise = np.tril(noise)
+        return m + noise + np.tril(noise, -1).T

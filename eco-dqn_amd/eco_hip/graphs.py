@@ -111,11 +111,18 @@ def edges_to_csr(n, i, j, w):
     return CSR(row_ptr, np.zeros(1, dtype=np.int64), _pack_edges(c, ww, fw), ww if fw else None)
 
 
-def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512):
+def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512, max_restarts=None):
     """Seeded synthetic graph pool built directly as CSR (no dense N x N per graph).
-    kind 'ER': G(n, p=param); 'BA': preferential attachment with m=param.
+    kind 'ER': G(n, p=param); 'BA': preferential attachment with m=param; 'REG': random d-regular with d=param
+    (max_restarts: see _regular_edges); 'WS': ring lattice with k=param.
     weights 'discrete' = fair +-1 per edge (EdgeType.DISCRETE), 'uniform' = 1, 'random' = float64 uniform in
     (-1, 1) (EdgeType.RANDOM; a float-weighted CSR with .weights)."""
+    if kind not in ("ER", "BA", "REG", "WS"):
+        raise ValueError(kind)
+    if kind in ("REG", "WS"):
+        param = _integer_param(kind, n, param)
+    if max_restarts is None:
+        max_restarts = _lib.ECO_REGULAR_MAX_RESTARTS
     rng = np.random.default_rng(seed)
     fw = weights == "random"
     wparts = []
@@ -132,8 +139,10 @@ def random_csr(kind, n_graphs, n, param, seed, weights="discrete", chunk=512):
                 iu, ju = iu_all[keep], ju_all[keep]
             elif kind == "BA":
                 iu, ju = _ba_edges(n, int(param), rng)
+            elif kind == "REG":
+                iu, ju = _regular_edges(n, param, rng, max_restarts)
             else:
-                raise ValueError(kind)
+                iu, ju = _ring_edges(n, param)
             if fw:
                 w = rng.uniform(-1.0, 1.0, iu.size)
                 w[w == 0.0] = 2.0 ** -53   # stored weights are nonzero
@@ -169,11 +178,88 @@ def _ba_edges(n, m, rng):
     return np.array(iu, dtype=np.int64), np.array(ju, dtype=np.int64)
 
 
+def _integer_param(kind, n, param):
+    """The degree d of 'REG' (0 <= d < n, n d even) or the k of 'WS' (0 <= k <= n) as an int; ValueError otherwise
+    (the checks eco_graphs_generate makes before a launch)."""
+    p = int(param)
+    if p != param:
+        raise ValueError(f"{kind} needs an integer parameter, got {param!r}")
+    if kind == "REG":
+        if not 0 <= p < n:
+            raise ValueError(f"regular-graph degree d={p} must be in [0, n={n})")
+        if (n * p) % 2:
+            raise ValueError(f"no {p}-regular graph on {n} vertices: n d must be even")
+    elif not 0 <= p <= n:
+        raise ValueError(f"ring-lattice k={p} must be in [0, n={n}]")
+    return p
+
+
+REGULAR_MAX_STALLS = 64   # kRegularMaxStalls of csrc/eco_graphgen.hip
+
+
+def _regular_edges(n, d, rng, max_restarts=_lib.ECO_REGULAR_MAX_RESTARTS):
+    """Edges (iu < ju) of a random simple d-regular graph: the pairing algorithm of networkx.random_regular_graph
+    (Steger and Wormald) restated, the algorithm of regular_kernel (csrc/eco_graphgen.hip) on numpy's stream.
+    An attempt starts from the stub list (every vertex d times) and runs rounds: shuffle the stubs, pair
+    consecutive ones, accept a pair that is neither a loop nor an edge already (this round's included), count the
+    stubs of a rejected pair as potential.  When no two distinct potential vertices are left that are not joined,
+    the attempt has failed and restarts from scratch; otherwise the next round runs on the potential stubs, until
+    none is left.  A round that adds no edge is a stall; an attempt with more than REGULAR_MAX_STALLS of them
+    fails too, which bounds the rounds of an attempt by n d / 2 + REGULAR_MAX_STALLS + 1.  More than max_restarts
+    restarts raise ValueError (likely only for d close to n - 1)."""
+    for _ in range(max_restarts + 1):
+        edges = set()
+        stubs = np.tile(np.arange(n, dtype=np.int64), d)
+        stalls = 0
+        while stubs.size:
+            rng.shuffle(stubs)
+            pot = np.zeros(n, dtype=np.int64)
+            before = len(edges)
+            for a, b in zip(stubs[0::2].tolist(), stubs[1::2].tolist()):
+                key = min(a, b) * n + max(a, b)
+                if a != b and key not in edges:
+                    edges.add(key)
+                else:
+                    pot[a] += 1
+                    pot[b] += 1
+            pv = np.flatnonzero(pot)
+            if pv.size == 0:
+                break
+            # a joinable pair is left iff some potential vertex is joined to fewer than all other potential ones
+            if not any(min(u, v) * n + max(u, v) not in edges
+                       for x, u in enumerate(pv.tolist()) for v in pv[:x].tolist()):
+                stubs = None
+                break
+            stalls += len(edges) == before
+            if stalls > REGULAR_MAX_STALLS:
+                stubs = None
+                break
+            stubs = np.repeat(pv, pot[pv])
+        if stubs is not None:
+            keys = np.fromiter(sorted(edges), dtype=np.int64, count=len(edges))
+            return keys // n, keys % n
+    raise ValueError(f"no {d}-regular graph on {n} vertices after {max_restarts} restarts of the pairing algorithm")
+
+
+def _ring_edges(n, k):
+    """Edges (iu < ju) of the ring lattice networkx.watts_strogatz_graph(n, k, 0): i ~ j iff their circular
+    distance min(|i - j|, n - |i - j|) is in [1, k // 2]."""
+    iu, ju = np.triu_indices(n, 1)
+    dist = np.minimum(ju - iu, n - (ju - iu))
+    keep = dist <= k // 2
+    return iu[keep], ju[keep]
+
+
 def edge_cap(kind, n, param, slack_sd=10.0):
-    """Edge-slot size per graph for on-device generation: exact for BA (2 m (N - m)),
-    mean + slack_sd standard deviations for ER."""
+    """Edge-slot size per graph for on-device generation: exact for BA (2 m (N - m)), REG (N d) and WS
+    (N min(2 (k // 2), N - 1): k // 2 = N / 2 reaches the antipode from both sides, one neighbour), mean +
+    slack_sd standard deviations for ER."""
     if kind == "BA":
         return 2 * int(param) * (n - int(param))
+    if kind == "REG":
+        return n * _integer_param(kind, n, param)
+    if kind == "WS":
+        return n * min(2 * (_integer_param(kind, n, param) // 2), n - 1)
     pairs = n * (n - 1) / 2.0
     mean, sd = 2.0 * pairs * param, 2.0 * np.sqrt(pairs * param * (1 - param))
     return int(mean + slack_sd * sd + 64)
@@ -249,19 +335,22 @@ class GraphStore:
 
     @classmethod
     def generated(cls, kind, n_graphs, n, param, seed=0, weights="discrete", device="cuda"):
-        """Pool of n_graphs ER(n, p=param) / BA(n, m=param) graphs generated on the device."""
+        """Pool of n_graphs ER(n, p=param) / BA(n, m=param) / REG(n, d=param) / WS(n, k=param) graphs generated
+        on the device."""
         st = cls.slots(n_graphs, n, edge_cap(kind, n, param), device=device, weights=weights)
         st.generate(0, n_graphs, kind, param, seed, weights)
         return st
 
     def generate(self, first, count, kind, param, seed, weights="discrete", stream=None, check=True):
         """Regenerate graphs [first, first+count) in place on the device (eco_graphs_generate);
-        check=True synchronises and raises on an edge-slot overflow."""
+        check=True synchronises and raises on an edge-slot overflow (or a 'REG' graph out of restarts).
+        kind 'ER' (param p), 'BA' (m), 'REG' (random d-regular, d) or 'WS' (ring lattice, k)."""
         if not hasattr(self, "cap"):
             raise ValueError("generate() needs a store created with GraphStore.slots()")
         ws = torch.empty(_lib.lib.eco_graphs_generate_workspace_bytes(self.n_spins, count), dtype=torch.uint8,
                          device=self.device)
-        k = {"ER": _lib.ECO_GRAPH_ER, "BA": _lib.ECO_GRAPH_BA}[kind]
+        k = {"ER": _lib.ECO_GRAPH_ER, "BA": _lib.ECO_GRAPH_BA, "REG": _lib.ECO_GRAPH_REGULAR,
+             "WS": _lib.ECO_GRAPH_WS}[kind]
         wk = {"uniform": _lib.ECO_WEIGHTS_UNIFORM, "discrete": _lib.ECO_WEIGHTS_DISCRETE,
               "random": _lib.ECO_WEIGHTS_RANDOM}[weights]
         if (weights == "random") != self.float_weights:

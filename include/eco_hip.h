@@ -148,8 +148,24 @@ size_t eco_graphs_adjbits_bytes(int32_t n_spins, int32_t n_graphs);
  * utils.py:137-148): w = 2u - 1 with u a 53-bit draw of the counter generator keyed by (seed, graph, unordered
  * pair), so the matrix is symmetric by construction; needs gs->edge_weights (written like `edges`), and the
  * packed byte holds sign(w).
+ * kind REGULAR, param = d (RandomRegularGraphGenerator, utils.py:238-275): a simple d-regular graph by the
+ * pairing algorithm of networkx.random_regular_graph (shuffle the stub list, pair consecutive stubs, keep the
+ * pairs that are neither loops nor edges, repeat on the stubs of the rejected pairs; an attempt with no joinable
+ * pair left restarts from scratch).  d an integer, 0 <= d < N, N d even, edge_cap >= N d, and the lists of one
+ * graph (2 N d + 2 N + 1 int32) within one workgroup's LDS: ECO_ERR_ARG otherwise, before any launch.  An attempt
+ * also fails after more than 64 rounds that add no edge, so it has at most N d / 2 + 65 rounds, and it is
+ * restarted at most ECO_REGULAR_MAX_RESTARTS times; a graph that exhausts them is left empty and reported like
+ * an overflow.  That does not happen at degrees well below N - 1 (about one restart per graph); close to N - 1
+ * restarts grow quickly (N = 12, d = 10: up to 52 seen in 1000 graphs) and the cap can trigger: such degrees are
+ * outside what the tests cover.
+ * kind WS, param = k (RandomWattsStrogatzGraphGenerator, utils.py:277-314): the ring lattice of
+ * networkx.watts_strogatz_graph(N, k, 0), vertex i joined to every j != i at circular distance <= k / 2 (integer
+ * division: an odd k gives (k - 1) / 2 neighbours per side; k = N is the complete graph).  k an integer,
+ * 0 <= k <= N, edge_cap >= the exact edge count N min(2 (k / 2), N - 1).  The reference always passes a
+ * rewiring probability of 0; rewiring with p > 0 is not implemented.
  * Runs eco_graphs_prepare afterwards.  An edge-slot overflow is reported by eco_check_errors. */
-enum { ECO_GRAPH_ER = 1, ECO_GRAPH_BA = 2 };
+enum { ECO_GRAPH_ER = 1, ECO_GRAPH_BA = 2, ECO_GRAPH_REGULAR = 3, ECO_GRAPH_WS = 4 };
+enum { ECO_REGULAR_MAX_RESTARTS = 256 };
 enum { ECO_WEIGHTS_UNIFORM = 0, ECO_WEIGHTS_DISCRETE = 1, ECO_WEIGHTS_RANDOM = 2 };
 size_t eco_graphs_generate_workspace_bytes(int32_t n_spins, int32_t count);
 int eco_graphs_generate(eco_graph_set *gs, int32_t first, int32_t count, int32_t kind, double param,
