@@ -238,6 +238,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && WLDS ? 2 : 1)) void mpnn_forwa
   const int c16 = lane & 15;
   const uint32_t* __restrict__ edges = a.gs.edges;
   const double* __restrict__ ewts = a.gs.edge_weights;  // FW only
+  if constexpr (!SAVE) {  // every graph of the block explores: the draw alone, no forward
+    if (act_skip_block<NW>(a, blk, g_valid, R0)) return;
+  }
 
   // ---- staging: x rows (WLDS, 8-float rows), row info, Wf ----
   const bool xwide = a.xw == 16;  // features 8..15 (read from global memory, never staged)
@@ -896,6 +899,9 @@ __global__ __launch_bounds__(64 * NW, 2) void mpnn_forward_large_kernel(MpnnArgs
   const int ntiles = rows_pad >> 4;
   const size_t R0 = (size_t)e * N;
   const size_t RT = (size_t)a.B * N;
+  if constexpr (!SAVE) {  // the episode explores: the draw alone, no forward
+    if (act_skip_block<NW>(a, e, 1, R0)) return;
+  }
   // Linears on the exact bf16x3-split weight fragments streamed from L2 (no LDS weight staging: the
   // LDS holds only the readout scratch, so two episodes share a CU and hide each other's gathers)
   const uint16_t* BFP = reinterpret_cast<const uint16_t*>(a.P + PK_BF);
@@ -1489,7 +1495,7 @@ int eco::kernel_paths() { return g_kernel_paths.load(std::memory_order_relaxed);
 
 extern "C" int32_t eco_set_kernel_paths(int32_t mask) {
   return g_kernel_paths.exchange(mask & (ECO_PATH_NO_DENSE | ECO_PATH_NO_DL | ECO_PATH_NO_SHARED | ECO_PATH_NO_PAIR |
-                                         ECO_PATH_DENSE2_FWD));
+                                         ECO_PATH_DENSE2_FWD | ECO_PATH_NO_ACT_SKIP));
 }
 
 // The kernel family of one MPNN call (ECO_ROUTE_* of include/eco_hip.h).  The forward, the pair forward and the
@@ -1516,6 +1522,15 @@ static int mpnn_route(const MpnnArgs& a, int paths, bool training) {
 static bool pair_fused(const MpnnArgs& a, int family, int paths) {
   return (family == ECO_ROUTE_DENSE3 || family == ECO_ROUTE_DENSE2) && a.gpb == 1 && a.gs.adjbits &&
          !(paths & ECO_PATH_NO_PAIR);
+}
+
+// Whether the blocks of a single forward whose graphs all drew "explore" return before their forward
+// (act_skip_block): only where the actions are the launch's one output -- no Q, no saved activations -- and a draw
+// can say "explore" at all (epsilon > 0: the greedy calls of the evaluator, the solvers and the train step never
+// skip).  The shared-graph family runs every episode through common launches and has no per-episode forward to skip.
+static bool act_skips(const MpnnArgs& a, int family, int paths, bool save) {
+  return a.has_act && !a.q && !save && a.act.epsilon > 0.f && family != ECO_ROUTE_SHARED && family != ECO_ROUTE_NONE &&
+         !(paths & ECO_PATH_NO_ACT_SKIP);
 }
 
 extern "C" int32_t eco_mpnn_route(const eco_graph_set* gs, int32_t n_obs_in, int32_t batch, int32_t gpb,
@@ -1677,6 +1692,7 @@ static int forward_setup(MpnnArgs* a, const FwdHead* h, int n, int32_t n_obs_in,
   family = mpnn_route(a[0], paths, saved != nullptr);
   fused = n == 2 && pair_fused(a[0], family, paths);
   if (n == 2 && !fused) return ECO_OK;
+  if (n == 1) a[0].act_skip = act_skips(a[0], family, paths, saved != nullptr);  // the pair kernels never skip
   if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg)
     call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)workspace);
   return ECO_OK;

@@ -411,6 +411,9 @@ __global__ __launch_bounds__(64 * DN_NW, 1) void mpnn_forward_dense2_kernel(Mpnn
   const uint16_t* PH = reinterpret_cast<const uint16_t*>(P + PK_FH);
   const int s4 = lane >> 4;
   const int c16 = lane & 15;
+  if constexpr (!SAVE && NNET == 1) {  // every graph of the block explores: the draw alone, no forward
+    if (act_skip_block<NW>(a, blk, g_valid, R0)) return;
+  }
 
   const bool has_tile = w < ntiles;
   const int r = w * 16 + c16;

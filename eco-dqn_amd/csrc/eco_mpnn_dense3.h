@@ -375,6 +375,9 @@ __global__ __launch_bounds__(64 * D3_NW, 1) void mpnn_forward_dense3_kernel(Mpnn
   const uint16_t* PH = reinterpret_cast<const uint16_t*>(P + PK_FH);
   const int s4 = lane >> 4;
   const int c16 = lane & 15;
+  if constexpr (!SAVE && NNET == 1) {  // every graph of the block explores: the draw alone, no forward
+    if (act_skip_block<NW>(a, blk, g_valid, R0)) return;
+  }
 
   const bool act = 2 * w < ntiles;  // the wave computes both of its tiles (a padding tile on zeros)
   int tl[2], r[2];

@@ -17,6 +17,7 @@ struct MpnnArgs {
   float* q;              // [B*N] or null
   float* sv;             // saved activations (training forward) or null
   int has_act;
+  int act_skip;          // inference act launch whose all-explore blocks return before their forward (act_skip_block)
   eco_act_config act;
   int32_t* actions;
   int32_t* err;          // device error word (eco_check_errors)
@@ -291,8 +292,83 @@ __device__ __forceinline__ void readout_act(const MpnnArgs& a, const float* Hs, 
   graph_act<NW>(a, Qb, blk, g_valid, R0);
 }
 
-// epsilon-greedy act (dqn.py:453-465, :490-512) of the block's graphs from their q values in LDS (Qb [rows]):
-// wave w handles graphs w, w + NW, ...
+// The epsilon-greedy act (dqn.py:453-465, :490-512) in two halves, each run by a whole wave for one graph (episode e,
+// feature rows from row0 = R0 + gl * N): the draw -- the explore decision and the random allowed vertex, functions of
+// (seed, counter, e) and the allowed-vertex column only -- and the greedy argmax over the graph's q values.
+
+// number of allowed vertices: all of them in a reversible env, else the rows whose first feature is allowed_value
+__device__ __forceinline__ int act_count_allowed(const MpnnArgs& a, size_t row0) {
+  if (a.act.reversible) return a.N;
+  const int lane = threadIdx.x & 63;
+  int n = 0;
+  for (int v0 = 0; v0 < a.N; v0 += 64) {
+    const int v = v0 + lane;
+    n += __popcll(__ballot(v < a.N && a.x[(row0 + v) * a.xw] == a.act.allowed_value));
+  }
+  return n;
+}
+
+// random.uniform(0,1) >= eps -> greedy (dqn.py:455); an episode without an allowed vertex stays greedy
+__device__ __forceinline__ bool act_explores(const MpnnArgs& a, int e, int n_allowed) {
+  const uint64_t r0 = rng3(a.act.seed, a.act.counter, (uint64_t)e);
+  return u01(r0) < a.act.epsilon && n_allowed > 0;
+}
+
+// the exploring episode's action: the k-th allowed vertex, k uniform in [0, n_allowed)
+__device__ __forceinline__ int act_random_vertex(const MpnnArgs& a, int e, size_t row0, int n_allowed) {
+  const int lane = threadIdx.x & 63;
+  const int N = a.N;
+  const uint64_t r1 = rng3(a.act.seed ^ 0xA5A5A5A5ull, a.act.counter, (uint64_t)e);
+  int k = (int)(r1 % (uint64_t)n_allowed);
+  if (a.act.reversible) return k;
+  int action = -1;
+  for (int v0 = 0; v0 < N && action < 0; v0 += 64) {
+    const int v = v0 + lane;
+    const bool al = v < N && a.x[(row0 + v) * a.xw] == a.act.allowed_value;
+    const uint64_t bal = __ballot(al);
+    const int c = __popcll(bal);
+    if (k < c) {
+      uint64_t b = bal;
+      for (int i = 0; i < k; ++i) b &= b - 1;
+      action = v0 + __ffsll((long long)b) - 1;
+    } else {
+      k -= c;
+    }
+  }
+  return action;
+}
+
+// the greedy action from the graph's q values Qg [N] (LDS): first index of the max over the allowed vertices (torch
+// argmax); n_allowed: their number
+__device__ __forceinline__ int act_greedy_vertex(const MpnnArgs& a, const float* Qg, size_t row0, int& n_allowed) {
+  const int lane = threadIdx.x & 63;
+  const int N = a.N;
+  float bestq = -INFINITY;
+  int besti = 0x7fffffff;
+  n_allowed = 0;
+  for (int v0 = 0; v0 < N; v0 += 64) {
+    const int v = v0 + lane;
+    bool allowed = false;
+    float qv = -INFINITY;
+    if (v < N) {
+      qv = Qg[v];
+      allowed = a.act.reversible || (a.x[(row0 + v) * a.xw] == a.act.allowed_value);
+    }
+    n_allowed += __popcll(__ballot(allowed));
+    if (allowed && (qv > bestq || (qv == bestq && v < besti))) { bestq = qv; besti = v; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float oq = __shfl_xor(bestq, o, 64);
+    const int oi = __shfl_xor(besti, o, 64);
+    if (oq > bestq || (oq == bestq && oi < besti)) { bestq = oq; besti = oi; }
+  }
+  // no allowed vertex (irreversible episode with every spin flipped): the reference's
+  // masked_fill(-10000).argmax over an all-masked row returns index 0 (dqn.py:416-428, :505-511)
+  return besti == 0x7fffffff ? 0 : besti;
+}
+
+// epsilon-greedy act of the block's graphs from their q values in LDS (Qb [rows]): wave w handles graphs w, w + NW, ...
 template <int NW>
 __device__ __forceinline__ void graph_act(const MpnnArgs& a, const float* Qb, int blk, int g_valid, size_t R0) {
   const int lane = threadIdx.x & 63;
@@ -300,55 +376,35 @@ __device__ __forceinline__ void graph_act(const MpnnArgs& a, const float* Qb, in
   const int N = a.N;
   for (int gl = w; gl < g_valid; gl += NW) {
     const int e = blk * a.gpb + gl;
-    float bestq = -INFINITY;
-    int besti = 0x7fffffff;
-    int n_allowed = 0;
-    for (int v0 = 0; v0 < N; v0 += 64) {
-      const int v = v0 + lane;
-      bool allowed = false;
-      float qv = -INFINITY;
-      if (v < N) {
-        qv = Qb[gl * N + v];
-        allowed = a.act.reversible || (a.x[(R0 + gl * N + v) * a.xw] == a.act.allowed_value);
-      }
-      n_allowed += __popcll(__ballot(allowed));
-      if (allowed && (qv > bestq || (qv == bestq && v < besti))) { bestq = qv; besti = v; }
-    }
-    // first index of the max (torch argmax)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float oq = __shfl_xor(bestq, o, 64);
-      const int oi = __shfl_xor(besti, o, 64);
-      if (oq > bestq || (oq == bestq && oi < besti)) { bestq = oq; besti = oi; }
-    }
-    // no allowed vertex (irreversible episode with every spin flipped): the reference's
-    // masked_fill(-10000).argmax over an all-masked row returns index 0 (dqn.py:416-428, :505-511)
-    int action = besti == 0x7fffffff ? 0 : besti;
-    const uint64_t r0 = rng3(a.act.seed, a.act.counter, (uint64_t)e);
-    if (u01(r0) < a.act.epsilon && n_allowed > 0) {  // random.uniform(0,1) >= eps -> greedy
-      const uint64_t r1 = rng3(a.act.seed ^ 0xA5A5A5A5ull, a.act.counter, (uint64_t)e);
-      int k = (int)(r1 % (uint64_t)n_allowed);
-      if (a.act.reversible) {
-        action = k;
-      } else {
-        action = -1;  // k-th allowed vertex
-        for (int v0 = 0; v0 < N && action < 0; v0 += 64) {
-          const int v = v0 + lane;
-          const bool al = v < N && a.x[(R0 + gl * N + v) * a.xw] == a.act.allowed_value;
-          const uint64_t bal = __ballot(al);
-          const int c = __popcll(bal);
-          if (k < c) {
-            uint64_t b = bal;
-            for (int i = 0; i < k; ++i) b &= b - 1;
-            action = v0 + __ffsll((long long)b) - 1;
-          } else {
-            k -= c;
-          }
-        }
-      }
-    }
+    const size_t row0 = R0 + (size_t)gl * N;
+    int n_allowed;
+    int action = act_greedy_vertex(a, Qb + gl * N, row0, n_allowed);
+    if (act_explores(a, e, n_allowed)) action = act_random_vertex(a, e, row0, n_allowed);
     if (lane == 0) a.actions[e] = action;
   }
+}
+
+// The act of a block whose graphs all explore, without their forward (the reference runs no network for a random
+// action, dqn.py:282): called at kernel entry by every wave, before any staging or barrier.  Each wave evaluates the
+// draws of ALL the block's graphs, so the answer is the same in every wave and none reaches a barrier the others
+// skipped.  True: the actions are written and the block is done; false (some graph is greedy, or the launch does
+// not skip: a.act_skip, set by the host for launches whose only output is the actions): nothing is written.
+template <int NW>
+__device__ __forceinline__ bool act_skip_block(const MpnnArgs& a, int blk, int g_valid, size_t R0) {
+  if (!a.act_skip) return false;
+  const int N = a.N;
+  for (int gl = 0; gl < g_valid; ++gl) {
+    const bool ex = act_explores(a, blk * a.gpb + gl, act_count_allowed(a, R0 + (size_t)gl * N));
+    if (!uniform_i(ex)) return false;
+  }
+  const int w = uniform_i(threadIdx.x >> 6);
+  for (int gl = w; gl < g_valid; gl += NW) {
+    const int e = blk * a.gpb + gl;
+    const size_t row0 = R0 + (size_t)gl * N;
+    const int action = act_random_vertex(a, e, row0, act_count_allowed(a, row0));
+    if ((threadIdx.x & 63) == 0) a.actions[e] = action;
+  }
+  return true;
 }
 
 }  // namespace eco

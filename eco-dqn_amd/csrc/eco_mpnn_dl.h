@@ -184,6 +184,9 @@ __global__ __launch_bounds__(64 * DL_NW, 1) void mpnn_forward_dl_kernel(MpnnArgs
   uint16_t* PL0 = sPL;
   uint16_t* PL1 = sPL + DL_PLANE;
   int* TE = sTE;
+  if constexpr (!SAVE) {  // the episode explores: the draw alone, no forward
+    if (act_skip_block<NW>(a, blk, 1, R0)) return;
+  }
 
   // ---- staging: Wf (LDS-DMA); per tile the row norm, adjacency operand and node features ----
   const int gid = a.gids[blk];  // first: the staging loads depend on it (waiting for it leaves the DMA in flight)

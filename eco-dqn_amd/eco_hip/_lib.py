@@ -38,6 +38,7 @@ ECO_WEIGHTS_UNIFORM, ECO_WEIGHTS_DISCRETE, ECO_WEIGHTS_RANDOM = 0, 1, 2   # eco_
 ECO_LOSS_MSE, ECO_LOSS_HUBER = 0, 1   # eco_dqn_td_loss loss kinds
 # kernel-path policy bits (eco_set_kernel_paths)
 ECO_PATH_NO_DENSE, ECO_PATH_NO_DL, ECO_PATH_NO_SHARED, ECO_PATH_NO_PAIR, ECO_PATH_DENSE2_FWD = 1, 2, 4, 8, 16
+ECO_PATH_NO_ACT_SKIP = -(1 << 31)   # the sign bit: all-explore act workgroups run their forward anyway (A/B, tests)
 # kernel families (eco_mpnn_route); PAIR_FUSED is or-ed in when a pair call runs both networks in one launch
 ECO_ROUTE_NONE, ECO_ROUTE_DENSE3, ECO_ROUTE_DENSE2, ECO_ROUTE_DL, ECO_ROUTE_SHARED, ECO_ROUTE_LARGE, \
     ECO_ROUTE_CSR = range(7)

@@ -330,8 +330,16 @@ int eco_mpnn_forward_pair(const float *packed_a, const float *packed_b, int32_t 
  *   DENSE2_FWD -- dense-aggregation forwards and backwards (N <= 224 blocks) run the one-tile-per-wave 16-wave
  *                 kernels instead of the two-tiles-per-wave 8-wave ones (bitwise the same results; A/B and
  *                 cross-check).
+ * One more bit picks no family and changes no result at all:
+ *   NO_ACT_SKIP -- an epsilon-greedy act launch (act given, epsilon > 0, q and saved NULL) runs the forward of every
+ *                  workgroup.  By default a workgroup whose episodes all drew "explore" (a function of the act
+ *                  config's seed and counter, the episode index and the allowed-vertex count, not of Q) writes their
+ *                  random actions and returns before its forward, as the reference runs no network for a random
+ *                  action (dqn.py:282); the actions are bit-identical either way.  It is the sign bit, apart from
+ *                  the family bits 0 .. 30.
  * The library reads no environment variables; this call is the only switch. Returns the previous mask. */
-enum { ECO_PATH_NO_DENSE = 1, ECO_PATH_NO_DL = 2, ECO_PATH_NO_SHARED = 4, ECO_PATH_NO_PAIR = 8, ECO_PATH_DENSE2_FWD = 16 };
+enum { ECO_PATH_NO_DENSE = 1, ECO_PATH_NO_DL = 2, ECO_PATH_NO_SHARED = 4, ECO_PATH_NO_PAIR = 8, ECO_PATH_DENSE2_FWD = 16,
+       ECO_PATH_NO_ACT_SKIP = -2147483647 - 1 };
 int32_t eco_set_kernel_paths(int32_t mask);
 
 /* Which kernel family the MPNN dispatcher picks under the current eco_set_kernel_paths mask (no reference
