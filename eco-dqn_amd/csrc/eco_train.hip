@@ -291,10 +291,14 @@ __global__ void colsum_jobs_kernel(ColJobs jobs) {
 // HUBER: smooth_l1_loss(beta = 1) instead of mse_loss (dqn.py:172): per-sample loss 0.5 d^2 for |d| < 1, else
 // |d| - 0.5; gradient d / B clamped to +-1 / B.  The comparisons are torch's own (x < -beta, x > beta, else
 // x), so a NaN d stays NaN in dq and in the loss.
-template <bool HUBER>
+// PRIO (eco_dqn_td_weighted, prioritised replay): the per-sample loss and the gradient are multiplied by the
+// importance weight is_w[b] (nullable: 1) -- the gradient as (w * g) / B, one rounding after an exact product when
+// w and g are short -- and abs_td[b] (nullable) receives |q(s,a) - td| whatever the loss kind.  PRIO = false is
+// the kernel as it was: eco_dqn_td_loss and a weighted call without weights and abs_td launch that instantiation.
+template <bool HUBER, bool PRIO>
 __global__ void td_kernel(const float* q_s, const float* q_tn, const int32_t* a_star, const int32_t* actions,
                           const float* rewards, const float* dones, int B, int N, float gamma, int clip,
-                          float* dq, float* sqerr) {
+                          float* dq, float* sqerr, const float* is_w, float* abs_td) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)B * N) return;
   const int b = (int)(i / N), j = (int)(i - (size_t)b * N);
@@ -311,6 +315,19 @@ __global__ void td_kernel(const float* q_s, const float* q_tn, const int32_t* a_
   const float td = rewards[b] + (1.f - dones[b]) * gamma * qt;
   const float q = q_s[i];
   const float diff = q - td;
+  if (PRIO) {
+    const float w = is_w ? is_w[b] : 1.f;
+    const float ad = fabsf(diff);
+    if (abs_td) abs_td[b] = ad;
+    if (HUBER) {
+      dq[i] = w * (diff < -1.f ? -1.f : diff > 1.f ? 1.f : diff) / (float)B;
+      sqerr[b] = w * (ad < 1.f ? 0.5f * diff * diff : ad - 0.5f);
+    } else {
+      dq[i] = w * (2.f * diff) / (float)B;
+      sqerr[b] = w * (diff * diff);
+    }
+    return;
+  }
   if (HUBER) {
     const float ad = fabsf(diff);
     dq[i] = (diff < -1.f ? -1.f : diff > 1.f ? 1.f : diff) / (float)B;  // smooth_l1_loss(reduction='mean') backward
@@ -617,25 +634,14 @@ __device__ __forceinline__ void compact_expand(const eco_env_config& cfg, const 
   }
 }
 
-// grid (2, M): blockIdx.x = 0 rebuilds s, 1 rebuilds s' of the m-th sampled transition.  The Feistel index x
-// names the slot the fp32 feature ring would read (replay_sample_kernel: slot x of a ring of `capacity`
-// written at k % capacity); here it is resolved to the transition k == x (mod capacity) among the newest
-// `size` and read from slot k % P.
-__global__ __launch_bounds__(256) void replay_compact_sample_kernel(eco_env_config cfg, CompactRing r, long long P,
-                                                                    int capacity, int size, long long pushed, int M,
-                                                                    uint64_t key, const double* tab, eco_graph_set gs,
-                                                                    float* xs, float* xn, int32_t* gid, int32_t* act,
-                                                                    float* rew, float* done) {
-  extern __shared__ uint32_t cr_lds[];
-  __shared__ int red[4];
-  const int m = blockIdx.y;
-  if (m >= M) return;
-  int bits = 2;
-  while ((1 << bits) < size) ++bits;
-  if (bits & 1) ++bits;
-  const int half = bits / 2;
-  uint32_t x = (uint32_t)m;
-  do { x = feistel(x, half, key); } while (x >= (uint32_t)size);
+// blockIdx.x = 0 rebuilds s, 1 rebuilds s' of the m-th minibatch row from the transition at LOGICAL position x:
+// the slot the fp32 feature ring would read (replay_sample_kernel: slot x of a ring of `capacity` written at
+// k % capacity); here it is resolved to the transition k == x (mod capacity) among the newest `size` and read
+// from slot k % P.  Shared by the uniform sampler and the gather by explicit position.
+__device__ __forceinline__ void compact_emit(const eco_env_config& cfg, const CompactRing& r, long long P, int capacity,
+                                             int size, long long pushed, int m, uint32_t x, const double* tab,
+                                             const eco_graph_set& gs, float* xs, float* xn, int32_t* gid, int32_t* act,
+                                             float* rew, float* done, uint32_t* cr_lds, int* red) {
   const long long base = pushed - size;  // oldest transition still held
   const long long k = base + (((long long)x - base % capacity) % capacity + capacity) % capacity;
   const long long slot = cr_slot(k, P);
@@ -676,6 +682,40 @@ __global__ __launch_bounds__(256) void replay_compact_sample_kernel(eco_env_conf
     __syncthreads();
   }
   compact_expand(cfg, cr_lds, r.ctx_n + slot * 4, mlr, tab, N, xn + (size_t)m * N * W, red);
+}
+
+// grid (2, M): the m-th of M distinct uniform positions (Feistel walk keyed by `key`, as replay_sample_kernel)
+__global__ __launch_bounds__(256) void replay_compact_sample_kernel(eco_env_config cfg, CompactRing r, long long P,
+                                                                    int capacity, int size, long long pushed, int M,
+                                                                    uint64_t key, const double* tab, eco_graph_set gs,
+                                                                    float* xs, float* xn, int32_t* gid, int32_t* act,
+                                                                    float* rew, float* done) {
+  extern __shared__ uint32_t cr_lds[];
+  __shared__ int red[4];
+  const int m = blockIdx.y;
+  if (m >= M) return;
+  int bits = 2;
+  while ((1 << bits) < size) ++bits;
+  if (bits & 1) ++bits;
+  const int half = bits / 2;
+  uint32_t x = (uint32_t)m;
+  do { x = feistel(x, half, key); } while (x >= (uint32_t)size);
+  compact_emit(cfg, r, P, capacity, size, pushed, m, x, tab, gs, xs, xn, gid, act, rew, done, cr_lds, red);
+}
+
+// grid (2, M): the transition at logical position idx[m] (DEVICE int32, each in [0, size); others are skipped)
+__global__ __launch_bounds__(256) void replay_compact_gather_kernel(eco_env_config cfg, CompactRing r, long long P,
+                                                                    int capacity, int size, long long pushed, int M,
+                                                                    const int32_t* idx, const double* tab,
+                                                                    eco_graph_set gs, float* xs, float* xn, int32_t* gid,
+                                                                    int32_t* act, float* rew, float* done) {
+  extern __shared__ uint32_t cr_lds[];
+  __shared__ int red[4];
+  const int m = blockIdx.y;
+  if (m >= M) return;
+  const int x = idx[m];
+  if ((unsigned)x >= (unsigned)size) return;  // never read outside the stored transitions
+  compact_emit(cfg, r, P, capacity, size, pushed, m, (uint32_t)x, tab, gs, xs, xn, gid, act, rew, done, cr_lds, red);
 }
 
 static size_t slab_bytes() { return (size_t)MAX_JOBS * SLABS_PER_JOB * SLAB * sizeof(float); }
@@ -791,10 +831,11 @@ extern "C" int eco_mpnn_grad_large(const float* packed, int32_t n_obs_in, const 
                     (float*)(ws + L.slabs), grad, st);
 }
 
-extern "C" int eco_dqn_td_loss(const float* q_s, const float* q_target_next, const int32_t* a_star,
-                               const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
-                               int32_t n_spins, float gamma, int32_t clip_q_targets, int32_t loss_kind, float* dq,
-                               float* sqerr, float* loss, eco_stream_t stream) {
+extern "C" int eco_dqn_td_weighted(const float* q_s, const float* q_target_next, const int32_t* a_star,
+                                   const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
+                                   int32_t n_spins, float gamma, int32_t clip_q_targets, int32_t loss_kind, float* dq,
+                                   float* sqerr, float* loss, const float* is_weights, float* abs_td,
+                                   eco_stream_t stream) {
   if (!q_s || !q_target_next || !a_star || !actions || !rewards || !dones || !dq || !sqerr || !loss)
     return fail(ECO_ERR_ARG, "null argument");
   if (batch < 1 || n_spins < 1) return fail(ECO_ERR_ARG, "bad batch/n_spins");
@@ -803,14 +844,28 @@ extern "C" int eco_dqn_td_loss(const float* q_s, const float* q_target_next, con
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)batch * n_spins;
   const unsigned nblk = (unsigned)((n + 255) / 256);
-  if (loss_kind == ECO_LOSS_HUBER)
-    td_kernel<true><<<nblk, 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma,
-                                          clip_q_targets, dq, sqerr);
-  else
-    td_kernel<false><<<nblk, 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma,
-                                           clip_q_targets, dq, sqerr);
+  const bool prio = is_weights || abs_td;
+#define ECO_TD_LAUNCH(H, P)                                                                                          \
+  td_kernel<H, P><<<nblk, 256, 0, st>>>(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma, \
+                                        clip_q_targets, dq, sqerr, is_weights, abs_td)
+  if (loss_kind == ECO_LOSS_HUBER) {
+    if (prio) ECO_TD_LAUNCH(true, true);
+    else ECO_TD_LAUNCH(true, false);
+  } else {
+    if (prio) ECO_TD_LAUNCH(false, true);
+    else ECO_TD_LAUNCH(false, false);
+  }
+#undef ECO_TD_LAUNCH
   mean_kernel<<<1, 256, 0, st>>>(sqerr, batch, loss);
   return check_launch("dqn_td");
+}
+
+extern "C" int eco_dqn_td_loss(const float* q_s, const float* q_target_next, const int32_t* a_star,
+                               const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
+                               int32_t n_spins, float gamma, int32_t clip_q_targets, int32_t loss_kind, float* dq,
+                               float* sqerr, float* loss, eco_stream_t stream) {
+  return eco_dqn_td_weighted(q_s, q_target_next, a_star, actions, rewards, dones, batch, n_spins, gamma,
+                             clip_q_targets, loss_kind, dq, sqerr, loss, nullptr, nullptr, stream);
 }
 
 extern "C" int eco_dqn_td(const float* q_s, const float* q_target_next, const int32_t* a_star,
@@ -915,19 +970,32 @@ extern "C" int eco_replay_compact_push(const eco_env_config* cfg, const void* en
   return check_launch("replay_compact_push");
 }
 
+// the checks and launch geometry shared by eco_replay_compact_sample and eco_replay_compact_gather
+static int compact_read_check(const eco_env_config* cfg, const void* env_state, const eco_graph_set* gs,
+                              int32_t env_batch, const void* ring, int32_t capacity, int32_t size, int64_t pushed,
+                              int32_t m, float* xs, float* xn, int32_t* graph_ids, int32_t* actions, float* rewards,
+                              float* dones) {
+  int rc = compact_check(cfg, env_batch, capacity);
+  if (rc) return rc;
+  if (!env_state || !gs || !ring || !xs || !xn || !graph_ids || !actions || !rewards || !dones)
+    return fail(ECO_ERR_ARG, "null argument");
+  if (m < 1 || size < 1 || size > capacity || pushed < size)
+    return fail(ECO_ERR_ARG, "replay sample: need m >= 1 and 1 <= size <= min(capacity, pushed)");
+  if (gs->n_spins != cfg->n_spins) return fail(ECO_ERR_ARG, "replay sample: graph set / env size mismatch");
+  if (gs->edge_weights) return fail(ECO_ERR_ARG, "compact replay: integer weights only (float-weighted graph set)");
+  return ECO_OK;
+}
+
 extern "C" int eco_replay_compact_sample(const eco_env_config* cfg, const void* env_state, const eco_graph_set* gs,
                                          int32_t env_batch, const void* ring, int32_t capacity, int32_t size,
                                          int64_t pushed, int32_t m, uint64_t seed, uint64_t counter, float* xs,
                                          float* xn, int32_t* graph_ids, int32_t* actions, float* rewards, float* dones,
                                          eco_stream_t stream) {
-  int rc = compact_check(cfg, env_batch, capacity);
+  const int rc = compact_read_check(cfg, env_state, gs, env_batch, ring, capacity, size, pushed, m, xs, xn, graph_ids,
+                                    actions, rewards, dones);
   if (rc) return rc;
-  if (!env_state || !gs || !ring || !xs || !xn || !graph_ids || !actions || !rewards || !dones)
-    return fail(ECO_ERR_ARG, "null argument");
-  if (size < m || m < 1 || size > capacity || pushed < size)
+  if (size < m)
     return fail(ECO_ERR_ARG, "replay sample: need m <= size <= min(capacity, pushed) (random.sample without replacement)");
-  if (gs->n_spins != cfg->n_spins) return fail(ECO_ERR_ARG, "replay sample: graph set / env size mismatch");
-  if (gs->edge_weights) return fail(ECO_ERR_ARG, "compact replay: integer weights only (float-weighted graph set)");
   const EnvLayout L = env_layout(cfg->n_spins, cfg->max_steps, env_batch);
   const double* tab = (const double*)((const uint8_t*)env_state + L.off_tab + 256);
   const long long P = (long long)capacity + env_batch;
@@ -939,4 +1007,23 @@ extern "C" int eco_replay_compact_sample(const eco_env_config* cfg, const void* 
       *cfg, compact_carve(const_cast<void*>(ring), cfg->n_spins, P), P, capacity, size, pushed, m,
       rng3(seed, counter, 0x5A5A), tab, *gs, xs, xn, graph_ids, actions, rewards, dones);
   return check_launch("replay_compact_sample");
+}
+
+extern "C" int eco_replay_compact_gather(const eco_env_config* cfg, const void* env_state, const eco_graph_set* gs,
+                                         int32_t env_batch, const void* ring, int32_t capacity, int32_t size,
+                                         int64_t pushed, int32_t m, const int32_t* idx, float* xs, float* xn,
+                                         int32_t* graph_ids, int32_t* actions, float* rewards, float* dones,
+                                         eco_stream_t stream) {
+  if (!idx) return fail(ECO_ERR_ARG, "replay gather: null idx");
+  const int rc = compact_read_check(cfg, env_state, gs, env_batch, ring, capacity, size, pushed, m, xs, xn, graph_ids,
+                                    actions, rewards, dones);
+  if (rc) return rc;
+  const EnvLayout L = env_layout(cfg->n_spins, cfg->max_steps, env_batch);
+  const double* tab = (const double*)((const uint8_t*)env_state + L.off_tab + 256);
+  const long long P = (long long)capacity + env_batch;
+  const int nt = cfg->n_spins <= 256 ? 64 : 128;  // as eco_replay_compact_sample
+  replay_compact_gather_kernel<<<dim3(2, m), nt, (size_t)cfg->n_spins * 4, (hipStream_t)stream>>>(
+      *cfg, compact_carve(const_cast<void*>(ring), cfg->n_spins, P), P, capacity, size, pushed, m, idx, tab, *gs, xs,
+      xn, graph_ids, actions, rewards, dones);
+  return check_launch("replay_compact_gather");
 }

@@ -123,6 +123,8 @@ _SIG = {
     "eco_mpnn_grad_large": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P, _P]),
     "eco_dqn_td": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
     "eco_dqn_td_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
+    "eco_dqn_td_weighted": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P, _P,
+                                           _P]),
     "eco_grad_clip": (ctypes.c_int, [_P, _I, ctypes.c_double, ctypes.c_double, _P, _P]),
     "eco_adam": (ctypes.c_int, [_P, _P, _P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int64, _P]),
@@ -137,6 +139,13 @@ _SIG = {
     "eco_replay_compact_sample": (ctypes.c_int, [ctypes.POINTER(EnvConfig), _P, ctypes.POINTER(GraphSet), _I, _P, _I,
                                                  _I, ctypes.c_int64, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P, _P,
                                                  _P]),
+    "eco_replay_compact_gather": (ctypes.c_int, [ctypes.POINTER(EnvConfig), _P, ctypes.POINTER(GraphSet), _I, _P, _I,
+                                                 _I, ctypes.c_int64, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "eco_prio_workspace_bytes": (ctypes.c_size_t, [_I]),
+    "eco_prio_push": (ctypes.c_int, [_P, _I, _I, _I, _I, _P, _P]),
+    "eco_prio_sample": (ctypes.c_int, [_P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, _P, _P, _P,
+                                       _P]),
+    "eco_prio_update": (ctypes.c_int, [_P, _I, _I, _P, _P, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
     "eco_per_create": (_P, [_I, ctypes.c_double, ctypes.c_double]),
     "eco_per_destroy": (None, [_P]),
     "eco_per_len": (_I, [_P]),

@@ -36,6 +36,7 @@ from ...parallel import allreduce_gradients_async, broadcast_parameters
 from .evaluation import Evaluator
 from .graph_slots import GraphSlotRing, graph_slots_needed  # noqa: F401  (graph_slots_needed: imported from here)
 from .learn_pipeline import LearnPipeline
+from .prioritised import DevicePrioritisedReplay, prioritised_config
 from .utils import CompactReplayBuffer, ReplayBuffer, TestMetric, set_global_seed
 
 
@@ -50,7 +51,7 @@ class DQN:
                  network_save_path='network', evaluate=True, test_envs=None, test_episodes=20,
                  test_frequency=10000, test_save_path='test_scores', test_metric=TestMetric.ENERGY_ERROR,
                  logging=True, seed=None, train_minibatch=None, graph_pool_ids=None, regenerate_graphs=None,
-                 compact_replay=None, target_sync="grad_steps", overlap_evaluation=True):
+                 compact_replay=None, target_sync="grad_steps", overlap_evaluation=True, prioritised_replay=None):
         if isinstance(envs, (list, tuple)):
             if len(envs) != 1:
                 raise NotImplementedError("pass one VecSpinSystem (it already holds B episodes)")
@@ -146,6 +147,14 @@ class DQN:
         else:
             self.replay_buffer = ReplayBuffer(replay_buffer_size, self.N, device=self.device, seed=self.seed,
                                               n_obs=envs.n_obs)
+        # prioritised_replay: None keeps the uniform ring above and today's train_step; a dict (alpha, beta0,
+        # beta_steps, eps, td_max; prioritised.PRIORITISED_DEFAULTS for missing keys) wraps whichever ring was chosen
+        # in proportional priorities on the device (prioritised.DevicePrioritisedReplay): importance-weighted TD
+        # loss, priorities updated from |td| right after it, no host read
+        self._prio = None
+        if prioritised_replay is not None:
+            self._prio = self.replay_buffer = DevicePrioritisedReplay(self.replay_buffer,
+                                                                      **prioritised_config(prioritised_replay))
         self.replay_ratio = minibatch_size / float(update_frequency)
         # reference (dqn.py:332-347): one train_step every update_frequency env-steps and one target sync every
         # update_target_frequency env-steps, i.e. a sync every update_target_frequency / update_frequency gradient
@@ -215,6 +224,8 @@ class DQN:
         self.dq = torch.empty(m, self.N, device=dev)
         self.sqerr = torch.empty(m, device=dev)
         self.loss_dev = torch.zeros(1, device=dev)
+        if self._prio is not None:
+            self.abs_td = torch.empty(m, device=dev)
         # above 512 vertices the gradient is one self-contained call (MPNN.grad_large) with one workspace; there is
         # no saved-activation buffer between a forward and a backward
         self._large = self.N > _lib.MPNN_MAX_SPINS
@@ -299,11 +310,26 @@ class DQN:
             scope_s = _lib.ECO_NORM_PER_CALL
         net.forward_graphs(xs, self.graphs, gid, norm_scope=scope_s, q_out=self.q_s, saved=self.saved)
         # TD error with the MSE or smooth-L1 (loss="huber", dqn.py:172) loss and its gradient
-        _lib.check(_lib.lib.eco_dqn_td_loss(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
-                                            _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
-                                            ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
-                                            self._loss_kind, _lib.ptr(self.dq), _lib.ptr(self.sqerr),
-                                            _lib.ptr(loss_dev), _lib.stream_ptr()))
+        if self._prio is None:
+            _lib.check(_lib.lib.eco_dqn_td_loss(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
+                                                _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
+                                                ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
+                                                self._loss_kind, _lib.ptr(self.dq), _lib.ptr(self.sqerr),
+                                                _lib.ptr(loss_dev), _lib.stream_ptr()))
+        else:
+            # prioritised replay: `transitions` is the buffer's last sample; its importance weights scale the loss
+            # and the gradient, and its |td| become the new priorities right here, before `overlap` prefetches the
+            # next minibatch: stream order makes minibatch k + 1 see minibatch k's priorities
+            w = self._prio.last_weights
+            if w is None or w.shape[0] != m:
+                raise ValueError("prioritised replay: train_step takes the replay buffer's last sample()")
+            _lib.check(_lib.lib.eco_dqn_td_weighted(_lib.ptr(self.q_s), _lib.ptr(self.q_tn), _lib.ptr(self.a_star),
+                                                    _lib.ptr(act), _lib.ptr(rew), _lib.ptr(done), m, self.N,
+                                                    ctypes.c_float(self.gamma), int(bool(self.clip_Q_targets)),
+                                                    self._loss_kind, _lib.ptr(self.dq), _lib.ptr(self.sqerr),
+                                                    _lib.ptr(loss_dev), _lib.ptr(w), _lib.ptr(self.abs_td),
+                                                    _lib.stream_ptr()))
+            self._prio.update(self.abs_td)
         if self._large:
             net.grad_large(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
         else:

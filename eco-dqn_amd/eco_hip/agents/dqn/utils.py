@@ -182,6 +182,9 @@ class PrioritisedReplayBuffer:
     under the same numpy seed it picks the same transitions; it returns (batch, weights [B, 1] on the
     device, buffer positions), batch being the stacked fields for add() rings or (xs, actions, rewards, xn,
     dones, graph_ids) for add_batch() rings.
+
+    The proportional buffer that lives on the device and plugs into DQN.learn() is
+    prioritised.DevicePrioritisedReplay.
     """
 
     def __init__(self, capacity=10000, alpha=0.7, beta0=0.5, device="cuda"):

@@ -420,6 +420,16 @@ int eco_dqn_td_loss(const float *q_s, const float *q_target_next, const int32_t 
                     int32_t clip_q_targets, int32_t loss_kind, float *dq, float *sqerr, float *loss,
                     eco_stream_t stream);
 
+/* eco_dqn_td_loss for prioritised replay: the same arguments plus the importance weights is_weights[batch] and an
+ * output abs_td[batch], both nullable.  With both NULL it IS eco_dqn_td_loss (the same kernel instantiation, bit for
+ * bit).  Otherwise the per-sample loss sqerr[b] and the dq entry of the taken action are multiplied by is_weights[b]
+ * (NULL: 1) -- loss = mean_b(w_b loss_b), dq = (w_b g_b) / B with g_b the unweighted 2 d or clamp(d, -1, 1) -- and
+ * abs_td[b] = |q_s[b][a_b] - td| whatever the loss kind: the new priorities of eco_prio_update. */
+int eco_dqn_td_weighted(const float *q_s, const float *q_target_next, const int32_t *a_star, const int32_t *actions,
+                        const float *rewards, const float *dones, int32_t batch, int32_t n_spins, float gamma,
+                        int32_t clip_q_targets, int32_t loss_kind, float *dq, float *sqerr, float *loss,
+                        const float *is_weights, float *abs_td, eco_stream_t stream);
+
 /* torch.nn.utils.clip_grad_norm_(network.parameters(), max_norm), norm type 2 (dqn.py:446-447), on the flat
  * gradient, between the gradient all-reduce and eco_adam:
  *   total_norm = grad_scale * sqrt(sum_i grad[i]^2),  coef = min(1, max_norm / (total_norm + 1e-6)),
@@ -497,6 +507,48 @@ int eco_replay_compact_sample(const eco_env_config *cfg, const void *env_state, 
                               int32_t env_batch, const void *ring, int32_t capacity, int32_t size, int64_t pushed,
                               int32_t m, uint64_t seed, uint64_t counter, float *xs, float *xn, int32_t *graph_ids,
                               int32_t *actions, float *rewards, float *dones, eco_stream_t stream);
+
+/* eco_replay_compact_sample by explicit position: DEVICE int32 idx[m], each the LOGICAL ring position x in
+ * [0, size) of a stored transition (transition k of the buffer's life sits at x = k % capacity -- the slot
+ * eco_replay_gather reads in a feature ring filled by the same pushes, so one idx gives one minibatch from either
+ * ring); duplicates allowed, m may exceed size; an x outside [0, size) leaves its output rows untouched. */
+int eco_replay_compact_gather(const eco_env_config *cfg, const void *env_state, const eco_graph_set *gs,
+                              int32_t env_batch, const void *ring, int32_t capacity, int32_t size, int64_t pushed,
+                              int32_t m, const int32_t *idx, float *xs, float *xn, int32_t *graph_ids,
+                              int32_t *actions, float *rewards, float *dones, eco_stream_t stream);
+
+/* Proportional prioritised replay on the device (Schaul et al. 2016), for the train loop that makes no host read.
+ * mass[capacity] (caller-owned DEVICE uint32, 16-byte aligned) holds one integer priority per LOGICAL ring position
+ * x = k % capacity (the x of eco_replay_gather / eco_replay_compact_gather):
+ *   mass = clamp(rint((min(|td|, td_max) + eps)^alpha * 2^16), 1, 2^31 - 1)   for a stored transition,
+ *   mass = 0                                                                  for a never-written position.
+ * Every sum is a uint64 (capacity * 2^31 < 2^63), so nothing depends on a reduction order: the sampler is
+ * deterministic and restated exactly on the CPU (tests/prio_common.py).  No atomics.  workspace: caller-owned
+ * device scratch of eco_prio_workspace_bytes(capacity) bytes (per-1024-entry block sums, their prefix, block maxima;
+ * recomputed by every call that needs them, nothing persists between calls).  Calls on one stream. */
+size_t eco_prio_workspace_bytes(int32_t capacity);   /* 0 for capacity < 1 */
+/* After a replay push of `batch` transitions at logical position pos (wrapping at capacity): their mass becomes the
+ * largest mass among the size_before positions stored before the push (a new transition has the highest priority,
+ * dqn/utils.py:127), or 2^16 -- the mass of priority p = 1, __get_max_td_err's value for an empty heap (:114-119) --
+ * when size_before = 0.  ECO_ERR_ARG before any launch unless 1 <= batch <= capacity, 0 <= pos < capacity,
+ * 0 <= size_before <= capacity. */
+int eco_prio_push(uint32_t *mass, int32_t capacity, int32_t pos, int32_t batch, int32_t size_before, void *workspace,
+                  eco_stream_t stream);
+/* Stratified proportional sample of m positions (with replacement: one large mass may own several strata) from the
+ * first `size` logical positions.  S = sum mass[0 .. size), q = S / m, r = S % m, lo_k = q k + (r k) / m,
+ * u_k = lo_k + rng3(seed, counter, k) % max(1, lo_{k+1} - lo_k)   (rng3: the counter RNG of eco_replay_sample),
+ * idx_out[k] (DEVICE int32) = the smallest x whose inclusive prefix sum exceeds u_k: a zero-mass position and a
+ * position >= size are never drawn.  weights_out[k] (DEVICE float32) = w_k / max_j w_j with
+ * w_k = (size * mass[x_k] / S)^(-beta) in float64 (dqn/utils.py:263-267).  S = 0 is a caller error (every stored
+ * transition has mass >= 1); the draws then stay inside [0, size).  ECO_ERR_ARG before any launch for size < 1,
+ * m < 1, m > 65536, size > capacity, a NULL or misaligned pointer, beta negative or not finite. */
+int eco_prio_sample(const uint32_t *mass, int32_t capacity, int32_t size, int32_t m, uint64_t seed, uint64_t counter,
+                    double beta, int32_t *idx_out, float *weights_out, void *workspace, eco_stream_t stream);
+/* mass[idx[k]] = the formula above of abs_td[k] (DEVICE float32; a NaN counts as td_max) for k < m; duplicate idx
+ * entries carry the same abs_td, so both writers store one value; an idx outside [0, capacity) is skipped.
+ * ECO_ERR_ARG before any launch for m < 1, alpha < 0, eps < 0, td_max <= 0 or a non-finite one. */
+int eco_prio_update(uint32_t *mass, int32_t capacity, int32_t m, const int32_t *idx, const float *abs_td, double alpha,
+                    double eps, double td_max, eco_stream_t stream);
 
 /* PrioritisedReplayBuffer (dqn/utils.py:86-277), rank-based: the binary max-heap of (buffer position,
  * td error) is a native HOST structure (every add / update is a sequential up-/down-heap walk) following
