@@ -620,8 +620,8 @@ __global__ void env_read_kernel(EnvArgs a, double* scalars, int8_t* spins, int8_
 // ------------------------------------------------------------------ host ----
 static int validate_cfg(const eco_env_config* c) {
   if (!c) return fail(ECO_ERR_ARG, "null env config");
-  if (c->n_spins < 1 || c->n_spins > ECO_MAX_SPINS)
-    return fail(ECO_ERR_ARG, "n_spins out of range [1, " + std::to_string(ECO_MAX_SPINS) + "]");
+  if (c->n_spins < 1 || c->n_spins > ECO_MAX_SPINS_WG)
+    return fail(ECO_ERR_ARG, "n_spins out of range [1, " + std::to_string(ECO_MAX_SPINS_WG) + "]");
   if (c->max_steps < 1 || c->max_steps > 32767) return fail(ECO_ERR_ARG, "max_steps out of range [1, 32767]");
   if (c->n_obs < 1 || c->n_obs > 13) return fail(ECO_ERR_ARG, "n_obs out of range [1, 13]");
   if (c->obs_ids[0] != ECO_OBS_SPIN_STATE)
@@ -645,6 +645,15 @@ static int validate_cfg(const eco_env_config* c) {
   if (c->float_weights && t != ECO_TARGET_CUT)
     return fail(ECO_ERR_ARG, "float edge weights run OptimisationTarget.CUT only (the generic-scorer kernels are "
                              "integer)");
+  // the workgroup-per-episode kernels (eco_env_wg.hip) are the integer MaxCut ones
+  if (c->n_spins > ECO_MAX_SPINS && c->float_weights)
+    return fail(ECO_ERR_ARG, "float edge weights run up to n_spins = " + std::to_string(ECO_MAX_SPINS) + " (" +
+                                 std::to_string(ECO_MAX_SPINS) + " < N <= " + std::to_string(ECO_MAX_SPINS_WG) +
+                                 " takes integer weights only)");
+  if (c->n_spins > ECO_MAX_SPINS && t != ECO_TARGET_CUT)
+    return fail(ECO_ERR_ARG, "the generic-scorer targets run up to n_spins = " + std::to_string(ECO_MAX_SPINS) + " (" +
+                                 std::to_string(ECO_MAX_SPINS) + " < N <= " + std::to_string(ECO_MAX_SPINS_WG) +
+                                 " runs OptimisationTarget.CUT only)");
   return ECO_OK;
 }
 
@@ -721,7 +730,7 @@ int eco::graphs_prepare_range(eco_graph_set* gs, int first, int count, hipStream
   } else {
     // one workgroup per graph holds row pointers, row sums and nonzero counts in LDS: 12 B per vertex,
     // so the graph set may have at most 160 KB / 12 B = 13,653 vertices (every env kernel stops at
-    // ECO_MAX_SPINS = 2048 anyway); larger sets are rejected here rather than failing at launch
+    // ECO_MAX_SPINS_WG = 8192 anyway: 96 KB); larger sets are rejected here rather than failing at launch
     const size_t lds = (size_t)(3 * gs->n_spins + 1) * sizeof(int);
     if (lds > (size_t)160 * 1024)
       return fail(ECO_ERR_ARG, "graphs_prepare: n_spins = " + std::to_string(gs->n_spins) +
@@ -786,6 +795,7 @@ extern "C" int eco_env_reset(const eco_env_config* cfg, const eco_graph_set* gs,
   const int blocks = (batch + 3) / 4;
   const size_t lds = (size_t)4 * cfg->n_spins;
   if (generic_target(cfg)) return env_reset_problem_launch(a, blocks, lds, st);
+  if (cfg->n_spins > ECO_MAX_SPINS) return env_reset_wg_launch(a, st);  // one workgroup per episode
   if (cfg->float_weights) ECO_DISPATCH_VPT(cfg->n_spins, (env_reset_kernel<V, double><<<blocks, 256, lds, st>>>(a)));
   else ECO_DISPATCH_VPT(cfg->n_spins, (env_reset_kernel<V><<<blocks, 256, lds, st>>>(a)));
   return check_launch("env_reset");
@@ -834,6 +844,7 @@ extern "C" int eco_env_step(const eco_env_config* cfg, const eco_graph_set* gs, 
                     cfg->obs_ids[4] == ECO_OBS_DISTANCE_FROM_BEST_STATE &&
                     cfg->obs_ids[5] == ECO_OBS_NUMBER_OF_QUALITY_IMPROVEMENTS &&
                     cfg->obs_ids[6] == ECO_OBS_TERMINATION_IMMANENCY;
+  if (cfg->n_spins > ECO_MAX_SPINS) return env_step_wg_launch(a, fast, st);  // one workgroup per episode
   if (cfg->float_weights) {  // f64 field and row deltas: [4 waves][N] f64 of LDS (64 KB at N = 2048)
     const size_t ldsw = (size_t)32 * cfg->n_spins;  // <= 64 KB: within the default dynamic LDS limit
     if (fast) ECO_DISPATCH_VPT(cfg->n_spins, (env_step_kernel<V, true, double><<<blocks, 256, ldsw, st>>>(a)));
@@ -861,6 +872,7 @@ extern "C" int eco_env_greedy_actions(const eco_env_config* cfg, const eco_graph
   const int blocks = (batch + 3) / 4;
   hipStream_t st = (hipStream_t)stream;
   if (generic_target(cfg)) return env_greedy_problem_launch(a, actions, blocks, (size_t)4 * cfg->n_spins, st);
+  if (cfg->n_spins > ECO_MAX_SPINS) return env_greedy_wg_launch(a, actions, st);  // one workgroup per episode
   if (cfg->float_weights)
     ECO_DISPATCH_VPT(cfg->n_spins, (env_greedy_kernel<V, double><<<blocks, 256, 0, st>>>(a, actions)));
   else

@@ -253,4 +253,10 @@ int env_reset_problem_launch(const EnvArgs& a, int blocks, size_t lds, hipStream
 int env_step_problem_launch(const EnvArgs& a, int blocks, size_t lds, hipStream_t st);
 int env_greedy_problem_launch(const EnvArgs& a, int32_t* actions, int blocks, size_t lds, hipStream_t st);
 
+// workgroup-per-episode launches (eco_env_wg.hip), ECO_MAX_SPINS < N <= ECO_MAX_SPINS_WG: one 256-thread block per
+// episode, OptimisationTarget.CUT with integer weights; fast: the DEFAULT_OBSERVABLES fp32-only observation write
+int env_reset_wg_launch(const EnvArgs& a, hipStream_t st);
+int env_step_wg_launch(const EnvArgs& a, bool fast, hipStream_t st);
+int env_greedy_wg_launch(const EnvArgs& a, int32_t* actions, hipStream_t st);
+
 }  // namespace eco

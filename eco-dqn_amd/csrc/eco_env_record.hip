@@ -2,8 +2,9 @@
 // (Network.reset / Network.step of src/agents/solver.py:198-216, :249-265).
 //
 // One 64-lane wave owns one episode, four episodes per workgroup, as in the env kernels; lane l walks
-// vertices l, l + 64, ... in a loop, so one instantiation serves every N up to ECO_MAX_SPINS (nothing is
-// kept per vertex across the loop, unlike the step kernels' register-resident fields).  The kernel only
+// vertices l, l + 64, ... in a loop, so one instantiation serves every N up to ECO_MAX_SPINS_WG (nothing is
+// kept per vertex across the loop, unlike the step kernels' register-resident fields; the state layout is the same
+// for the workgroup-per-episode env above ECO_MAX_SPINS, which is CUT with integer weights).  The kernel only
 // reads the env state: the row's values are those the step kernels already keep --
 //   solution    the value the step kernels store as best_solution when a state becomes the best one
 //               (CUT: score - |lb|, MIN_CUT: qn - score, set problems: n1 if valid, else N / 0);
@@ -143,8 +144,12 @@ extern "C" int eco_env_record(const eco_env_config* cfg, const eco_graph_set* gs
   if (B < 1) return fail(ECO_ERR_ARG, "batch must be >= 1");
   if (!state) return fail(ECO_ERR_ARG, "null state");
   const int N = cfg->n_spins, tgt = cfg->optimisation_target;
-  if (N < 1 || N > ECO_MAX_SPINS)
-    return fail(ECO_ERR_ARG, "n_spins out of range [1, " + std::to_string(ECO_MAX_SPINS) + "]");
+  if (N < 1 || N > ECO_MAX_SPINS_WG)
+    return fail(ECO_ERR_ARG, "n_spins out of range [1, " + std::to_string(ECO_MAX_SPINS_WG) + "]");
+  // above ECO_MAX_SPINS the env is the integer MaxCut one (eco_env_wg.hip); the recorder's vertex loops take any N
+  if (N > ECO_MAX_SPINS && (tgt != ECO_TARGET_CUT || cfg->float_weights || (gs && gs->edge_weights)))
+    return fail(ECO_ERR_ARG, std::to_string(ECO_MAX_SPINS) + " < N <= " + std::to_string(ECO_MAX_SPINS_WG) +
+                                 " runs OptimisationTarget.CUT with integer weights only");
   if (cfg->max_steps < 1 || cfg->max_steps > 32767) return fail(ECO_ERR_ARG, "max_steps out of range [1, 32767]");
   if (tgt < ECO_TARGET_CUT || tgt > ECO_TARGET_MIN_DOM_SET || tgt == ECO_TARGET_ENERGY)
     return fail(ECO_ERR_TARGET, "Invalid optimization target: " + std::to_string(tgt) + " and biased False");

@@ -1748,6 +1748,65 @@ extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco
   }
 }
 
+// ---- inference above MPNN_MAX_SPINS_LARGE vertices: a self-contained entry on mpnn_forward_large_kernel ----
+// The kernel keeps an episode's rows in global memory and walks them in loops bounded by N alone, so it runs
+// 2048 < N <= ECO_MAX_SPINS_WG unchanged (DESIGN section 22 has the audit: pack_row_info's 16-bit row length and
+// 15-bit norm hold up to 32767 neighbours; the readout scratch is 512 + 4 + rows_pad floats = 34.8 KB at 8192; every
+// episode offset into the workspace, obs_x and q is a size_t product; per-episode row offsets r * 64 stay below
+// 2^19).  eco_mpnn_forward and eco_mpnn_route keep their range: this entry has its own workspace layout -- the
+// 256 B header (call max degree; the shared-graph key slot, zeroed by the kernel) and three [rows_pad][64] f32 row
+// buffers per episode -- and never takes the shared-graph path, whose tables are one LDS block.
+static bool forward_wg_range(int32_t n_spins) { return n_spins > MPNN_MAX_SPINS_LARGE && n_spins <= ECO_MAX_SPINS_WG; }
+static const char* kForwardWgRange = "eco_mpnn_forward_wg takes 2048 < N <= 8192";
+
+extern "C" size_t eco_mpnn_forward_wg_workspace_bytes(int32_t n_spins, int32_t batch, int32_t n_obs_in) {
+  if (!forward_wg_range(n_spins) || batch < 1 || n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return 0;
+  const size_t rows_pad = ((size_t)n_spins + 15) & ~(size_t)15;
+  if ((size_t)batch * rows_pad > (size_t)INT32_MAX / 64) return 0;  // the 32-bit row index
+  return 256 + (size_t)batch * rows_pad * 64 * 3 * sizeof(float);
+}
+
+extern "C" int eco_mpnn_forward_wg(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                                   const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope,
+                                   float* q, const eco_act_config* act, int32_t* actions, void* workspace,
+                                   eco_stream_t stream) {
+  if (!packed || !gs || !graph_ids || !obs_x || !workspace)
+    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": null argument");
+  if (!gs->row_ptr || !gs->edge_base || !gs->edges || !gs->deg || !gs->max_deg)
+    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": incomplete graph set");
+  if (!forward_wg_range(gs->n_spins))
+    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + " (got N = " + std::to_string(gs->n_spins) +
+                                 "); eco_mpnn_forward is the forward up to 2048 vertices");
+  if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return fail(ECO_ERR_ARG, "n_obs_in out of range [1, 16]");
+  if (batch < 1) return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": batch must be >= 1");
+  if (gs->n_graphs < 1) return fail(ECO_ERR_ARG, "empty graph set");
+  if (gs->edge_weights)
+    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + " with integer weights only (float-weighted sets run up "
+                                                            "to 2048 vertices)");
+  const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;
+  if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
+  if (norm_scope != ECO_NORM_PER_GRAPH && norm_scope != ECO_NORM_PER_CALL) return fail(ECO_ERR_ARG, "bad norm_scope");
+  if (act && !actions) return fail(ECO_ERR_ARG, "act config without actions buffer");
+  if (!q && !act) return fail(ECO_ERR_ARG, "nothing to compute (q and act both null)");
+  if (eco_mpnn_forward_wg_workspace_bytes(gs->n_spins, batch, n_obs_in) == 0)
+    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": batch * rows beyond the 32-bit row index ((2^31 - 1) / 64)");
+  hipStream_t st = (hipStream_t)stream;
+  MpnnArgs a{};
+  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = gs->n_spins; a.gpb = 1;
+  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
+  a.err = err_word();
+  a.call_maxdeg = (int*)workspace;
+  a.q = q;
+  a.has_act = act != nullptr;
+  if (act) a.act = *act;
+  a.actions = actions;
+  // all-explore workgroups skip their forward only where the actions are the one output (act_skips)
+  a.act_skip = a.has_act && !q && a.act.epsilon > 0.f && !(kernel_paths() & ECO_PATH_NO_ACT_SKIP);
+  if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg)
+    call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)workspace);
+  return launch_large(a, workspace, st);
+}
+
 size_t eco::mpnn_grad_ws_bytes(int32_t n_spins, int32_t batch) {
   if (n_spins < 1 || batch < 1) return 0;
   const int gpb = graphs_per_block(n_spins, batch);

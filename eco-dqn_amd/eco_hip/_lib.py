@@ -28,7 +28,8 @@ ECO_TARGET_CUT, ECO_TARGET_ENERGY, ECO_TARGET_MIN_COVER, ECO_TARGET_MIN_CUT, ECO
 def obs_x_stride(n_obs):
     """ECO_OBS_X_STRIDE: floats per node-feature row of obs_x."""
     return 8 if n_obs <= 8 else 16
-ECO_MAX_SPINS = 2048
+ECO_MAX_SPINS = 2048          # wave-per-episode env kernels, eco_mpnn_forward, training, float weights, generic scorers
+ECO_MAX_SPINS_WG = 8192       # workgroup-per-episode env kernels and eco_mpnn_forward_wg: CUT, integer weights, inference
 MPNN_MAX_SPINS = 512          # saved-activation training (eco_mpnn_backward) up to here; eco_mpnn_grad_large above
 ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS)
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
@@ -113,6 +114,9 @@ _SIG = {
     "eco_mpnn_workspace_bytes": (ctypes.c_size_t, [_I, _I]),
     "eco_mpnn_forward": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _I, _P,
                                         ctypes.POINTER(ActConfig), _P, _P, _P, _P]),
+    "eco_mpnn_forward_wg_workspace_bytes": (ctypes.c_size_t, [_I, _I, _I]),
+    "eco_mpnn_forward_wg": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _I, _P,
+                                           ctypes.POINTER(ActConfig), _P, _P, _P]),
     "eco_mpnn_forward_pair": (ctypes.c_int, [_P, _P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _I, _P,
                                              ctypes.POINTER(ActConfig), _P, _P, ctypes.POINTER(ActConfig), _P, _P,
                                              _P]),

@@ -66,6 +66,12 @@ class DQN:
                     or not math.isfinite(max_grad_norm) or max_grad_norm <= 0):
                 raise ValueError("max_grad_norm must be None or a finite positive number")
             max_grad_norm = float(max_grad_norm)
+        if envs.graphs.n_spins > _lib.ECO_MAX_SPINS:
+            # the gradient (eco_mpnn_grad_large) and the training forwards stop at ECO_MAX_SPINS; above it the env and
+            # the network run inference and search only (solvers, test_network)
+            raise ValueError(f"DQN trains on graphs of at most ECO_MAX_SPINS={_lib.ECO_MAX_SPINS} vertices, got N = "
+                             f"{envs.graphs.n_spins}: {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} is inference "
+                             "and search only")
         self.loss = loss
         self._loss_kind = _lib.ECO_LOSS_HUBER if loss == "huber" else _lib.ECO_LOSS_MSE
         self.max_grad_norm = max_grad_norm

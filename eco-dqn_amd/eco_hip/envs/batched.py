@@ -46,6 +46,16 @@ def make_config(n_spins, max_steps, observables=DEFAULT_OBSERVABLES, reward_sign
     if float_weights and optimisation_target != OptimisationTarget.CUT:
         raise ValueError(f"float edge weights (EdgeType.RANDOM) run OptimisationTarget.CUT only, not "
                          f"{optimisation_target}: the generic-scorer kernels are integer")
+    if n_spins > _lib.ECO_MAX_SPINS_WG:
+        raise ValueError(f"n_spins = {n_spins} exceeds ECO_MAX_SPINS_WG={_lib.ECO_MAX_SPINS_WG}")
+    if n_spins > _lib.ECO_MAX_SPINS:   # the workgroup-per-episode kernels: integer MaxCut
+        rng = f"{_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG}"
+        if float_weights:
+            raise ValueError(f"float edge weights run up to n_spins = {_lib.ECO_MAX_SPINS}, got {n_spins}: {rng} takes "
+                             "integer weights only")
+        if optimisation_target != OptimisationTarget.CUT:
+            raise ValueError(f"{optimisation_target} runs up to n_spins = {_lib.ECO_MAX_SPINS}, got {n_spins}: {rng} "
+                             "runs OptimisationTarget.CUT only")
     c = _lib.EnvConfig()
     c.n_spins = n_spins
     c.max_steps = max_steps

@@ -297,8 +297,12 @@ class GraphStore:
             e = np.ascontiguousarray(edges, dtype=np.uint32).view(np.int32)
             self.edges = torch.from_numpy(e if e.size else np.zeros(1, np.int32)).to(dev)
         self.n_spins = n1 - 1
-        if self.n_spins > _lib.ECO_MAX_SPINS:
-            raise ValueError(f"N={self.n_spins} exceeds ECO_MAX_SPINS={_lib.ECO_MAX_SPINS}")
+        if self.n_spins > _lib.ECO_MAX_SPINS_WG:
+            raise ValueError(f"N={self.n_spins} exceeds ECO_MAX_SPINS_WG={_lib.ECO_MAX_SPINS_WG}")
+        if self.n_spins > _lib.ECO_MAX_SPINS and self.float_weights:
+            raise ValueError(f"a float-weighted store holds at most ECO_MAX_SPINS={_lib.ECO_MAX_SPINS} vertices, got "
+                             f"N={self.n_spins}: {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} takes integer "
+                             "weights only")
         self.deg = torch.zeros(self.n_graphs, self.n_spins, dtype=torch.int32, device=dev)
         self.max_deg = torch.zeros(self.n_graphs, dtype=torch.int32, device=dev)
         self.meta = torch.zeros(self.n_graphs, 4, dtype=torch.float64, device=dev)

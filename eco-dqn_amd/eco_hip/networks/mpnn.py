@@ -109,7 +109,10 @@ class MPNN(torch.nn.Module):
             raise ValueError(f"obs_x must be a contiguous float32 [B, N, {w}] tensor for n_obs_in={self.n_obs_in}")
 
     def _workspace(self, n_spins, batch):
-        need = _lib.lib.eco_mpnn_workspace_bytes(n_spins, batch)
+        if n_spins > _lib.ECO_MAX_SPINS:   # eco_mpnn_forward_wg's own layout (0: a size it rejects with its message)
+            need = max(256, _lib.lib.eco_mpnn_forward_wg_workspace_bytes(n_spins, batch, self.n_obs_in))
+        else:
+            need = _lib.lib.eco_mpnn_workspace_bytes(n_spins, batch)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.flat.device)
         return self._ws
@@ -129,10 +132,19 @@ class MPNN(torch.nn.Module):
         if self.timer is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        _lib.check(_lib.lib.eco_mpnn_forward(
-            _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-            _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
-            _lib.ptr(actions_out), _lib.ptr(saved), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
+        if N > _lib.ECO_MAX_SPINS:   # inference above 2048 vertices: eco_mpnn_forward_wg, picked by N alone
+            if saved is not None:
+                raise ValueError(f"training forward (saved activations) supports N <= {_lib.MPNN_MAX_SPINS}; inference "
+                                 f"runs {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG}, got N = {N}")
+            _lib.check(_lib.lib.eco_mpnn_forward_wg(
+                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
+                _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
+                _lib.ptr(actions_out), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
+        else:
+            _lib.check(_lib.lib.eco_mpnn_forward(
+                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
+                _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
+                _lib.ptr(actions_out), _lib.ptr(saved), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
         if self.timer is not None:
             ev[1].record()
             self.timer.append((ev[0], ev[1], B, graph_ids))

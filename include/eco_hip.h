@@ -64,7 +64,13 @@ enum { ECO_TARGET_CUT = 1, ECO_TARGET_ENERGY = 2, ECO_TARGET_MIN_COVER = 3, ECO_
 #define ECO_MPNN_MAX_OBS 16 /* MPNN n_obs_in limit; node-feature rows are ECO_OBS_X_STRIDE(n_obs_in) floats */
 /* obs_x row width in floats for n_obs observables: 8 up to 8 observables, else 16 */
 #define ECO_OBS_X_STRIDE(n_obs) ((n_obs) <= 8 ? 8 : 16)
-#define ECO_MAX_SPINS 2048 /* largest N the env kernels take (wave-per-episode, 32 vertices per lane) */
+#define ECO_MAX_SPINS 2048 /* largest N the wave-per-episode env kernels take (32 vertices per lane); also the limit of
+                              eco_mpnn_forward / eco_mpnn_route, of training, of float-weighted sets and of the
+                              generic-scorer targets */
+#define ECO_MAX_SPINS_WG 8192 /* largest N of the env (spinsystem.py has no size limit): ECO_MAX_SPINS < N <=
+                                 ECO_MAX_SPINS_WG runs the workgroup-per-episode kernels (one 256-thread workgroup per
+                                 episode, 32 vertices per thread) -- OptimisationTarget.CUT with integer weights only,
+                                 inference and search (eco_mpnn_forward_wg); anything else is ECO_ERR_ARG */
 
 /* Env configuration: the kwargs of core.make("SpinSystem", gg, max_steps, **env_args)
  * (src/envs/core.py:3-10 -> spinsystem.py:29-48).  OptimisationTarget.CUT is the hot path (its own
@@ -175,7 +181,12 @@ int eco_graphs_generate(eco_graph_set *gs, int32_t first, int32_t count, int32_t
 /* ---- batched SpinSystem (spinsystem.py) ---- */
 
 /* Bytes of the opaque per-batch env state buffer (spins, local fields, counters,
- * best-so-far, visited-state sets).  A pure query of cfg (float_weights included) and batch. */
+ * best-so-far, visited-state sets).  A pure query of cfg (float_weights included) and batch.
+ * Every env entry below takes n_spins up to ECO_MAX_SPINS_WG and dispatches on it: up to ECO_MAX_SPINS the
+ * wave-per-episode kernels, above it the workgroup-per-episode ones (same state layout, same semantics;
+ * OptimisationTarget.CUT with integer weights -- a float-weighted set or a generic-scorer target above
+ * ECO_MAX_SPINS is ECO_ERR_ARG before any launch, and the query returns 0).  The visited-state sets take
+ * batch * (max_steps + 1) * ceil(n_spins / 64) * 8 bytes: 16.8 MB per episode at n_spins = 8192, max_steps = 16384. */
 size_t eco_env_state_bytes(const eco_env_config *cfg, int32_t batch);
 
 /* SpinSystemBase.reset (spinsystem.py:183-259, _reset_state :283-330).
@@ -309,6 +320,23 @@ size_t eco_mpnn_saved_bytes(int32_t n_spins, int32_t batch);
 int eco_mpnn_forward(const float *packed, int32_t n_obs_in, const eco_graph_set *gs, const int32_t *graph_ids,
                      int32_t batch, const float *obs_x, int32_t norm_scope, float *q, const eco_act_config *act,
                      int32_t *actions, void *saved, void *workspace, eco_stream_t stream);
+
+/* MPNN.forward (mpnn.py:40-77, no size limit) for 2048 < N <= ECO_MAX_SPINS_WG: inference in ONE self-contained
+ * entry, as eco_mpnn_grad_large is for training above 512 (eco_mpnn_forward and eco_mpnn_route keep their range
+ * N <= 2048).  The arguments of eco_mpnn_forward that inference uses, with the same meaning: norm scope (PER_GRAPH,
+ * PER_CALL, PER_CALL_REUSE), q[B][N] (nullable), the fused epsilon-greedy act / actions[B].  Each episode's rows live
+ * in global memory (one workgroup per episode, the kernel of eco_mpnn_forward's LARGE family); the shared-graph path
+ * is not taken.  8- and 16-float observation rows; integer weights (a float-weighted set is ECO_ERR_ARG).
+ * workspace: eco_mpnn_forward_wg_workspace_bytes(n_spins, batch, n_obs_in) bytes of scratch -- a 256 B header and
+ * three [rows_pad][64] f32 row buffers per episode (rows_pad = n_spins rounded up to 16): 6.3 MB per episode at 8192.
+ * The query returns 0 outside 2048 < n_spins <= 8192, for batch < 1, n_obs_in outside [1, 16] and when
+ * batch * rows_pad exceeds (2^31 - 1) / 64.  ECO_ERR_ARG before any launch, with a message naming
+ * "2048 < N <= 8192": N outside the range, a NULL pointer (q and act may not both be NULL; act needs actions),
+ * batch < 1, batch * rows_pad beyond the 32-bit row index. */
+size_t eco_mpnn_forward_wg_workspace_bytes(int32_t n_spins, int32_t batch, int32_t n_obs_in);
+int eco_mpnn_forward_wg(const float *packed, int32_t n_obs_in, const eco_graph_set *gs, const int32_t *graph_ids,
+                        int32_t batch, const float *obs_x, int32_t norm_scope, float *q, const eco_act_config *act,
+                        int32_t *actions, void *workspace, eco_stream_t stream);
 
 /* Two networks on the same graphs and node features in one call: the double-DQN pair of dqn.py:416-428
  * (a = online net -> greedy argmax a* over s', b = target net -> Q(s') to gather at a*).  Equivalent to

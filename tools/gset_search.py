@@ -6,7 +6,7 @@ is absent from the reference, .MISSING_LARGE_BLOBS:1), one GPU's share of config
 beside the Greedy solver (src/agents/solver.py:88-131) from the all -1 state and from each attempt's random start.
 No best-known value exists for the stand-in ("parity unpinned"); G22's own best-known cut, 13359
 (_graphs/benchmarks/opts/cuts_gset_2000spin.pkl[0]), is a same-size, same-density reference point only.
-usage: python tools/gset_search.py [attempts] [seed]  -> one JSON line"""
+usage: python tools/gset_search.py [attempts] [seed] [n] [p] [weights]  -> one JSON line"""
 import json
 import os
 import sys
@@ -42,10 +42,12 @@ def env_args():
             'horizon_length': None, 'stag_punishment': None, 'basin_reward': None, 'reversible_spins': True}
 
 
-def search(attempts=1024, seed=0, n=2000, p=0.01, graph_seed=1234):
+def search(attempts=1024, seed=0, n=2000, p=0.01, graph_seed=1234, weights="uniform"):
+    """weights: "uniform" (G22-like) or "discrete" (+-1, as the G-set's toroidal and +-1 random instances); n up to
+    ECO_MAX_SPINS_WG = 8192."""
     from eco_hip.graphs import GraphStore
     from eco_hip.experiments import test_network
-    adj = GraphStore.random("ER", 1, n, p, seed=graph_seed, weights="uniform").dense(0)
+    adj = GraphStore.random("ER", 1, n, p, seed=graph_seed, weights=weights).dense(0)
     net = pretrained_er200()
     t0 = time.perf_counter()
     res, raw = test_network(net, env_args(), [adj], step_factor=2, n_attempts=attempts, return_raw=True, seed=seed)
@@ -53,7 +55,7 @@ def search(attempts=1024, seed=0, n=2000, p=0.01, graph_seed=1234):
     r = res.iloc[0]
     cuts = np.asarray(raw["cuts"][0])
     return {
-        "workload": f"configs[4] G22-like stand-in ER({n}, {p}) unit weights, graph seed {graph_seed}: "
+        "workload": f"configs[4] G22-like stand-in ER({n}, {p}) {weights} weights, graph seed {graph_seed}: "
                     f"{attempts} attempts x T = {2 * n} (step_factor 2), pretrained ER-200 network",
         "edges": int((adj != 0).sum() // 2),
         "cut": float(r["cut"]), "cut_recomputed_from_sol": cut_of(adj, r["sol"]),
@@ -69,4 +71,11 @@ def search(attempts=1024, seed=0, n=2000, p=0.01, graph_seed=1234):
 if __name__ == "__main__":
     a = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
     s = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-    print(json.dumps(search(a, s)), flush=True)
+    kw = {}
+    if len(sys.argv) > 3:   # [n] [p] [weights]: another stand-in, e.g. 3000 0.001334 discrete (about 6000 +-1 edges)
+        kw["n"] = int(sys.argv[3])
+    if len(sys.argv) > 4:
+        kw["p"] = float(sys.argv[4])
+    if len(sys.argv) > 5:
+        kw["weights"] = sys.argv[5]
+    print(json.dumps(search(a, s, **kw)), flush=True)
