@@ -18,6 +18,13 @@ faithful "reference-cost" baseline:
 Pinned against the reference itself: tests/golden/make_golden.py imports the
 reference (identity numba.jit shim) and records trajectories; tests/test_oracle_golden.py
 checks this file against them bit for bit.
+
+Sparse mode (no counterpart in the reference): `SpinSystemOracle` also takes a `SparseMatrix`, a CSR
+triple `(row_ptr, col, val)` or an edge list `(n, i, j, w)` in place of the dense matrix, for sizes
+where an [N, N] float64 matrix and four dense products per step are too much (N = 8192: 512 MB).
+The weights must be integers: every sum below is then a sum of integers far below 2^53, exact in
+float64 in any order, so the sparse mode returns the dense mode's values bit for bit
+(tests/test_spinsystem_sparse_cpu.py).  Its observation carries no adjacency rows.
 """
 import numpy as np
 
@@ -37,13 +44,68 @@ DEFAULT_OBSERVABLES = [SPIN_STATE, IMMEDIATE_QUALITY_CHANGE, TIME_SINCE_FLIP,
 S2V_OBSERVABLES = [SPIN_STATE]          # experiments/train_eco.py:311-315
 
 
+class SparseMatrix:
+    """Symmetric integer-weighted matrix with a zero diagonal as CSR over the directed entries (u, v, a_uv)."""
+
+    def __init__(self, row_ptr, col, val):
+        self.row_ptr = np.asarray(row_ptr, dtype=np.int64).reshape(-1)
+        self.col = np.asarray(col, dtype=np.int64)
+        val = np.asarray(val)
+        assert np.array_equal(val, np.rint(val)), "sparse mode takes integer weights only"
+        self.val = val.astype(np.float64)
+        n = self.row_ptr.size - 1
+        self.shape = (n, n)
+        assert self.row_ptr[0] == 0 and self.row_ptr[-1] == self.col.size == self.val.size
+        self.row = np.repeat(np.arange(n), np.diff(self.row_ptr))
+        assert self.col.size == 0 or (0 <= self.col.min() and self.col.max() < n)
+        assert not np.any(self.row == self.col), "zero diagonal"
+        # symmetric, every entry once: the sorted (u, v, a) and (v, u, a) lists coincide
+        key, tkey = self.row * n + self.col, self.col * n + self.row
+        assert np.unique(key).size == key.size, "repeated entry"
+        o, t = np.argsort(key), np.argsort(tkey)
+        assert np.array_equal(key[o], tkey[t]) and np.array_equal(self.val[o], self.val[t]), "not symmetric"
+
+    @classmethod
+    def from_edges(cls, n, i, j, w):
+        """Undirected edge list, every edge once."""
+        i, j, w = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64), np.asarray(w)
+        r, c, v = np.concatenate([i, j]), np.concatenate([j, i]), np.concatenate([w, w])
+        order = np.lexsort((c, r))
+        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(r, minlength=n))])
+        return cls(row_ptr, c[order], v[order])
+
+    @classmethod
+    def from_dense(cls, matrix):
+        r, c = np.nonzero(matrix)
+        return cls(np.concatenate([[0], np.cumsum(np.bincount(r, minlength=matrix.shape[0]))]), c, matrix[r, c])
+
+    def matvec(self, x):
+        return np.bincount(self.row, weights=self.val * x[self.col], minlength=self.shape[0])
+
+
+def as_sparse(matrix):
+    """SparseMatrix of a SparseMatrix, a CSR triple (row_ptr, col, val) or an edge list (n, i, j, w); None for
+    anything else (a dense matrix)."""
+    if isinstance(matrix, SparseMatrix):
+        return matrix
+    if isinstance(matrix, tuple) and len(matrix) == 3:
+        return SparseMatrix(*matrix)
+    if isinstance(matrix, tuple) and len(matrix) == 4:
+        return SparseMatrix.from_edges(*matrix)
+    return None
+
+
 def calculate_cut(spins, matrix):
     """src/envs/utils.py:90-94"""
+    if isinstance(matrix, SparseMatrix):   # the same sum over the nonzero entries only
+        return (1 / 4) * np.sum(np.multiply(matrix.val, 1 - spins[matrix.row] * spins[matrix.col]))
     return (1 / 4) * np.sum(np.multiply(matrix, 1 - np.outer(spins, spins)))
 
 
 def calculate_cut_changes(spins, matrix):
     """src/envs/utils.py:97-102 (numba @jit upstream; identical values for integer weights)."""
+    if isinstance(matrix, SparseMatrix):
+        return spins * matrix.matvec(spins)
     return spins * (matrix @ spins)
 
 
@@ -80,7 +142,9 @@ class SpinSystemOracle:
                  horizon_length=None, stopping="NORMAL"):
         # spinsystem.py:116 -- first observable must be the spin state
         assert observables[0] == SPIN_STATE, "First observable must be Observation.SPIN_STATE."
-        self.matrix = np.asarray(matrix, dtype=np.float64)
+        sparse = as_sparse(matrix)
+        self.sparse = sparse is not None
+        self.matrix = sparse if self.sparse else np.asarray(matrix, dtype=np.float64)
         self.n_spins = self.matrix.shape[0]
         self.max_steps = max_steps
         self.observables = list(enumerate(observables))
@@ -95,7 +159,7 @@ class SpinSystemOracle:
 
     # ---- MaximumCutUnbiasedScorer (score_solver.py:343-419) ----
     def _set_normalisers(self):
-        J = self.matrix
+        J = self.matrix.val if self.sparse else self.matrix    # the zero entries add nothing to either sum
         self.qn = max(1, np.sum(np.multiply(J, (J > 0))) / 2)          # :353-357
         self.lb = min(0, np.sum(np.multiply(J, (J < 0))) / 2)          # :359-365
 
@@ -228,6 +292,8 @@ class SpinSystemOracle:
         state = self.state.copy()
         if self.spin_basis == "BINARY":
             state[0, :] = (1 - state[0, :]) / 2
+        if self.sparse:
+            return state
         return np.vstack((state, self.matrix))
 
     def state_rows(self):

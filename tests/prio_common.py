@@ -67,6 +67,77 @@ def sample(mass, size, m, seed, counter):
     return out
 
 
+def _u64(mass, size):
+    """mass[:size] as uint64, with the bound that keeps every prefix sum inside a uint64 (the kernels' own bound)."""
+    assert len(mass) * (1 << 31) < (1 << 63), "capacity * 2^31 must stay below 2^63"
+    v = np.asarray(mass[:size])
+    assert v.size == 0 or (int(v.min()) >= 0 and int(v.max()) <= PRIO_MAX)
+    return v.astype(np.uint64)
+
+
+def sample_fast(mass, size, m, seed, counter):
+    """sample() for rings of millions of entries: the prefix sums as one uint64 np.cumsum (exact: no sum reaches
+    2^63) and the search as np.searchsorted(side="right"), the array form of bisect_right.  Equal to sample()
+    entry for entry (tests/test_prio_cpu.py)."""
+    prefix = np.cumsum(_u64(mass, size), dtype=np.uint64)
+    S = int(prefix[-1])
+    assert S > 0, "no stored mass"
+    u = np.array(draws(S, m, seed, counter), dtype=np.uint64)
+    return np.searchsorted(prefix, u, side="right").astype(np.int64)
+
+
+def weights_fast(mass, size, idx, beta):
+    """weights() with the total as one uint64 sum: the same integer S, then the same float64 statements."""
+    S = np.float64(int(_u64(mass, size).sum(dtype=np.uint64)))
+    mk = np.asarray(mass)[np.asarray(idx, dtype=np.int64)].astype(np.float64)
+    w = np.power(np.float64(size) * mk / S, -np.float64(beta))
+    return (w / w.max()).astype(np.float32)
+
+
+def mass_pattern(pattern, size, capacity=5000):
+    """The mass patterns of tests/test_prio_gpu.py::test_sampler_is_exact (int64 array of `capacity` entries)."""
+    rng = np.random.default_rng(1000 * size + len(pattern))
+    if pattern == "equal":
+        mass = np.full(capacity, 777, np.int64)
+    elif pattern == "random":
+        mass = rng.integers(1, (1 << 20) + 1, capacity)
+    elif pattern == "zeros30":
+        mass = rng.integers(1, (1 << 20) + 1, capacity)
+        mass[rng.random(capacity) < 0.3] = 0
+        if mass[:size].sum() == 0:
+            mass[0] = 1          # a stored transition has mass >= 1: S = 0 is outside the contract
+    else:
+        mass = np.ones(capacity, np.int64)
+        mass[size // 2] = (1 << 31) - 1
+    return mass                  # positions >= size hold mass too: they must never be drawn
+
+
+def large_ring_pattern(pattern, size, capacity):
+    """Mass of a ring of `capacity` positions for the samplers' large-size tests (int64 array).  Positions >= size
+    hold mass too: they must never be drawn.
+      random   uniform in [1, 2^20]
+      zeros30  the same with 30 % of the positions at 0
+      tail     1 everywhere but the last 700 positions of [0, size), which hold 2^31 - 1: all but about 1 / 458,000
+               of the mass (size = 3,280,000; less below) sits there, so nearly every draw resolves in the last full
+               block and the final partial one
+      head     the mirror image: the first 700 positions"""
+    rng = np.random.default_rng(size + 7 * len(pattern))
+    if pattern in ("random", "zeros30"):
+        mass = rng.integers(1, (1 << 20) + 1, capacity)
+        if pattern == "zeros30":
+            mass[rng.random(capacity) < 0.3] = 0
+            mass[0] = max(int(mass[0]), 1)
+    elif pattern in ("tail", "head"):
+        mass = np.ones(capacity, np.int64)
+        if pattern == "tail":
+            mass[size - 700:size] = PRIO_MAX
+        else:
+            mass[:700] = PRIO_MAX
+    else:
+        raise ValueError(pattern)
+    return mass.astype(np.int64)
+
+
 def weights(mass, size, idx, beta):
     """w_k = (size * mass[x_k] / S)^(-beta) in float64 -- the product, then the quotient, then one pow, as the
     kernel orders them -- divided by the largest w of the minibatch, as float32."""

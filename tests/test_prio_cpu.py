@@ -91,6 +91,63 @@ def test_push_mass_and_weights_of_the_oracle():
     assert w[1] == 1.0 and w[0] == np.float32(1 / 3) and abs(float(w[2]) - 3 ** -0.5) < 1e-7
 
 
+@pytest.mark.parametrize("size", [1, 37, 1024, 1025, 5000])
+@pytest.mark.parametrize("pattern", ["equal", "random", "zeros30", "giant"])
+def test_fast_paths_equal_the_python_int_oracle(pattern, size):
+    """sample_fast / weights_fast (uint64 cumsum + searchsorted, what the large-ring GPU tests are judged by) against
+    sample / weights (Python ints) on the 5000-entry patterns of tests/test_prio_gpu.py: exactly equal."""
+    mass = pc.mass_pattern(pattern, size)
+    for m in (1, 64, 257):
+        for counter in (3, 4):
+            ref = pc.sample(mass, size, m, 0xC0FFEE, counter)
+            fast = pc.sample_fast(mass, size, m, 0xC0FFEE, counter)
+            assert fast.dtype == ref.dtype and np.array_equal(fast, ref), (pattern, size, m)
+            w, wf = pc.weights(mass, size, ref, 0.4), pc.weights_fast(mass, size, ref, 0.4)
+            assert wf.dtype == np.float32 and np.array_equal(w.view(np.int32), wf.view(np.int32))
+    with pytest.raises(AssertionError, match="2\\^63"):
+        pc.sample_fast(np.broadcast_to(np.int8(1), (1 << 32,)), 4, 1, 1, 1)   # capacity * 2^31 reaches 2^63
+
+
+def _sample_without_cross_wave_term(mass, size, m, seed, counter):
+    """sample_fast with the defect the 65,537-entry case guards against: prio_scan_kernel without its cross-wave
+    term `for k < w: acc += ws[k]`, so that the prefix restarts at block 64 (the first block of the second wave at
+    chunk = 1).  The total S is right: the kernel sums it separately."""
+    v = np.asarray(mass[:size]).astype(np.uint64)
+    prefix = np.cumsum(v, dtype=np.uint64)
+    S = int(prefix[-1])
+    cut = 64 * pc.PRIO_BLOCK
+    if size > cut:
+        prefix[cut:] -= prefix[cut - 1]
+    u = np.array(pc.draws(S, m, seed, counter), dtype=np.uint64)
+    return np.searchsorted(prefix, u, side="right").astype(np.int64)
+
+
+def test_oracle_notices_a_prefix_that_restarts_at_block_64():
+    cap = 3280000
+    for size, differs in ((65536, False), (65537, True)):
+        mass = pc.large_ring_pattern("tail", size, cap)
+        ref = pc.sample_fast(mass, size, 2048, 0xC0FFEE, 3)
+        bad = _sample_without_cross_wave_term(mass, size, 2048, 0xC0FFEE, 3)
+        # 65,537: position 65,536 holds 1 / 700 of the mass, 2.9 of the 2048 strata: the true sampler draws it, the
+        # restarted prefix (2^31 - 1 there, below every such draw) cannot
+        assert np.array_equal(ref, bad) != differs, size
+        if differs:
+            assert (ref == size - 1).sum() >= 2 and not (bad == size - 1).any()
+    assert ref.max() < size and (mass[ref] > 0).all()
+
+
+def test_large_ring_patterns():
+    cap = 3280000
+    for size in (65537, cap):
+        for pattern in ("tail", "head"):
+            mass = pc.large_ring_pattern(pattern, size, cap)
+            big = np.flatnonzero(mass == pc.PRIO_MAX)
+            assert big.size == 700 and (mass != pc.PRIO_MAX).sum() == cap - 700 and mass.min() == 1
+            assert (big[0], big[-1]) == ((size - 700, size - 1) if pattern == "tail" else (0, 699))
+        z = pc.large_ring_pattern("zeros30", size, cap)
+        assert 0.25 < (z == 0).mean() < 0.35 and z.max() <= 1 << 20
+
+
 def test_bad_arguments_are_rejected_before_any_launch():
     from eco_hip import _lib
     buf = (ctypes.c_uint32 * 64)()          # host memory: never touched, the checks come first

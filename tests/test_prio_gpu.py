@@ -27,20 +27,7 @@ def _u32(a):
 
 
 def _mass_pattern(pattern, size):
-    rng = np.random.default_rng(1000 * size + len(pattern))
-    if pattern == "equal":
-        mass = np.full(CAP, 777, np.int64)
-    elif pattern == "random":
-        mass = rng.integers(1, (1 << 20) + 1, CAP)
-    elif pattern == "zeros30":
-        mass = rng.integers(1, (1 << 20) + 1, CAP)
-        mass[rng.random(CAP) < 0.3] = 0
-        if mass[:size].sum() == 0:
-            mass[0] = 1          # a stored transition has mass >= 1: S = 0 is outside the contract
-    else:
-        mass = np.ones(CAP, np.int64)
-        mass[size // 2] = (1 << 31) - 1
-    return mass                  # positions >= size hold mass too: they must never be drawn
+    return pc.mass_pattern(pattern, size, CAP)   # shared with tests/test_prio_cpu.py
 
 
 def _sample(mass_dev, size, m, seed, counter, beta, ws):
@@ -87,6 +74,94 @@ def test_sampler_is_exact(pattern, size):
         assert not np.array_equal(a, b)                              # another counter: another draw
         np.testing.assert_array_equal(b, pc.sample(mass, size, 257, seed, 4))
     assert np.array_equal(md.cpu().numpy(), mass.astype(np.int32))   # the sampler writes no mass
+
+
+BIG_CAP = 3280000   # the ring of the training recipe: 3204 block sums, four per scan thread
+
+
+@pytest.mark.parametrize("size", [65536, 65537, 1048576, 1048577, BIG_CAP])
+@pytest.mark.parametrize("pattern", ["random", "zeros30", "tail", "head"])
+def test_sampler_is_exact_on_large_rings(pattern, size):
+    """Capacity 3,280,000.  nb = ceil(size / 1024) block sums: 64 (the last size one wave of prio_scan_kernel
+    covers), 65 (the first block whose prefix needs the cross-wave term `acc += ws[k]`), 1024 (chunk 1, every scan
+    thread busy), 1025 (chunk 2, threads 513 and up own nothing), 3204 (chunk 4); the draw's binary search runs over
+    up to 3204 prefixes.  Positions exact, weights within 4 ulp (the bar and the reasoning of the file docstring), the
+    mass unmodified, a repeated call bitwise equal, no position >= size drawn although those hold mass.
+
+    What 65,537 can and cannot show: the draw never READS the prefix of the last block (its search falls back on the
+    last block and subtracts bpre[nb - 2]), so a wrong bpre[64] alone passes there; blocks 64 and up of the three
+    larger sizes are read.  The oracle's own draws must reach them (asserted below, on the reference alone, for
+    "random" at m = 2048): at 1,048,576 a position in each of the 16 wave ranges of the scan and 1000 distinct
+    blocks; at the two larger sizes every wave range that owns a full block (8 and 13) and 1000 distinct blocks; and
+    "tail" at m = 2048 draws position size - 1, the lone entry of the last block at 65,537 and 1,048,577."""
+    from eco_hip import _lib
+    mass = pc.large_ring_pattern(pattern, size, BIG_CAP)
+    md = _u32(mass)
+    ws = torch.zeros(_lib.lib.eco_prio_workspace_bytes(BIG_CAP), dtype=torch.uint8, device="cuda")
+    seed, beta = 0xC0FFEE, 0.4
+    nb = (size + pc.PRIO_BLOCK - 1) // pc.PRIO_BLOCK
+    chunk = (nb + 1023) // 1024
+    for m in (1, 257, 2048):
+        idx, w = _sample(md, size, m, seed, 3, beta, ws)
+        ref = pc.sample_fast(mass, size, m, seed, 3)
+        assert ref.min() >= 0 and ref.max() < size and (mass[ref] > 0).all()
+        np.testing.assert_array_equal(idx, ref, err_msg=f"{pattern} size {size} m {m}")
+        wref = pc.weights_fast(mass, size, ref, beta)
+        d = _ulps(w, wref)
+        blocks = np.unique(ref // pc.PRIO_BLOCK)
+        waves = np.unique(blocks // chunk // 64)
+        print(f"{pattern} size {size} m {m}: max weight distance {int(d.max())} ulp, {len(blocks)} distinct blocks, "
+              f"{len(waves)} scan waves, {len(np.unique(ref))} distinct positions")
+        assert d.max() <= 4, (pattern, size, m, int(d.max()))
+        assert w.max() == 1.0 and w.min() > 0
+        idx2, w2 = _sample(md, size, m, seed, 3, beta, ws)
+        assert np.array_equal(idx, idx2) and np.array_equal(w.view(np.int32), w2.view(np.int32))
+        if pattern == "random" and m == 2048:
+            # wave ranges that own at least one full block (at 65 and 1025 blocks the last wave range owns one
+            # entry, which "tail" reaches below)
+            full = {64: 1, 65: 1, 1024: 16, 1025: 8, 3204: 13}[nb]
+            assert len(waves) >= full
+            assert len(blocks) >= (1000 if nb >= 1024 else 64)
+        if pattern == "tail" and m == 2048:
+            assert ref.max() == size - 1      # the last position, alone in its block at 65,537 and 1,048,577
+        if pattern in ("tail", "head") and m > 1:
+            # the 700 giants hold all but size / (700 * 2^31) < 3e-6 of the mass: at most the first and the last
+            # stratum can reach a one
+            giants = (ref >= size - 700) if pattern == "tail" else (ref < 700)
+            assert giants.sum() >= m - 2
+    assert np.array_equal(md.cpu().numpy(), mass.astype(np.int32))   # the sampler writes no mass
+
+
+def test_push_takes_the_maximum_of_more_than_256_blocks():
+    """prio_push_kernel's strided `b += 256` maximum over the block maxima: the single largest mass sits in block
+    292 (position 299,999 of 300,000 stored) and in block 2929 (position 3,000,000 of a full ring), both beyond the
+    first 256 block maxima that one pass of the 256 threads reads; then a larger mass beyond size_before, which must be
+    ignored.  The whole ring against pc.push."""
+    from eco_hip import _lib
+    ws = torch.zeros(_lib.lib.eco_prio_workspace_bytes(BIG_CAP), dtype=torch.uint8, device="cuda")
+    rng = np.random.default_rng(11)
+    base = rng.integers(1, 1 << 24, BIG_CAP)
+    giant = (1 << 30) + 12345
+    for size_before, at, pos, batch in ((300000, 299999, 300000, 48), (BIG_CAP, 3000000, BIG_CAP - 20, 48),
+                                        (300000, 300100, 300000, 48)):
+        mass = base.copy()
+        mass[at] = giant
+        md = _u32(mass)
+        rc = _lib.lib.eco_prio_push(_lib.ptr(md), BIG_CAP, pos, batch, size_before, _lib.ptr(ws), _lib.stream_ptr())
+        assert rc == _lib.ECO_OK, _lib.last_error()
+        torch.cuda.synchronize()
+        ref = mass.copy()
+        mx = pc.push(ref, pos, batch, size_before)
+        got = md.cpu().numpy().astype(np.int64)
+        np.testing.assert_array_equal(got, ref)
+        written = (np.arange(BIG_CAP) - pos) % BIG_CAP < batch
+        assert written.sum() == batch and (got[written] == mx).all()
+        if at < size_before:
+            assert mx == giant and at // pc.PRIO_BLOCK >= 256
+        else:
+            assert mx == mass[:size_before].max() < (1 << 24) and got[at] == giant   # not stored yet: ignored, kept
+        # the maximum is one entry, outside the first 256 blocks: a maximum over those alone is another value
+        assert mass[:256 * pc.PRIO_BLOCK].max() != mx or at >= size_before
 
 
 def test_push_wraps_and_takes_the_current_maximum():
