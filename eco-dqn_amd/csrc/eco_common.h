@@ -92,12 +92,15 @@ struct alignas(16) EpScal {
 struct EnvLayout {
   int N, T, B, words, cap;
   size_t off_tab, off_scal, off_spins, off_field, off_tsf, off_best, off_vidx, off_vhash, off_vstates, total;
+  size_t off_oinorm;  // generic scorers only (0 otherwise): the invalidity normaliser of each episode's reset rows
 };
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // float_weights: the resident local field is f64 (float-weighted graph sets); 0 keeps the integer layout byte for byte
-inline EnvLayout env_layout(int N, int T, int B, int float_weights = 0) {
+// generic: a generic-scorer target (not CUT) appends one f64 per episode, the normaliser its reset observation was
+// written with (the previous reset's, env_reset_problem_kernel); every other offset is unchanged
+inline EnvLayout env_layout(int N, int T, int B, int float_weights = 0, bool generic = false) {
   EnvLayout L;
   L.N = N; L.T = T; L.B = B;
   L.words = (N + 63) / 64;
@@ -115,6 +118,8 @@ inline EnvLayout env_layout(int N, int T, int B, int float_weights = 0) {
   L.off_vidx = o;    o = align_up(o + (size_t)B * cap * 4, 256);
   L.off_vhash = o;   o = align_up(o + (size_t)B * cap * 8, 256);
   L.off_vstates = o; o = align_up(o + (size_t)B * (size_t)(T + 1) * L.words * 8, 256);
+  L.off_oinorm = 0;
+  if (generic) { L.off_oinorm = o; o = align_up(o + sizeof(double) * (size_t)B, 256); }
   L.total = o;
   return L;
 }

@@ -758,7 +758,8 @@ extern "C" size_t eco_graphs_adjbits_bytes(int32_t n_spins, int32_t n_graphs) {
 
 extern "C" size_t eco_env_state_bytes(const eco_env_config* cfg, int32_t batch) {
   if (validate_cfg(cfg) != ECO_OK || batch < 1) return 0;
-  return env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights).total;
+  return env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights,
+                    cfg->optimisation_target != ECO_TARGET_CUT).total;
 }
 
 static int make_args(EnvArgs& a, const eco_env_config* cfg, const eco_graph_set* gs, void* state, int32_t batch) {
@@ -770,7 +771,7 @@ static int make_args(EnvArgs& a, const eco_env_config* cfg, const eco_graph_set*
   a = EnvArgs{};
   a.cfg = *cfg;
   if (gs) a.gs = *gs;
-  a.L = env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights);
+  a.L = env_layout(cfg->n_spins, cfg->max_steps, batch, cfg->float_weights, cfg->optimisation_target != ECO_TARGET_CUT);
   a.state = (uint8_t*)state;
   a.B = batch;
   a.err = err_word();

@@ -64,6 +64,72 @@ __device__ __forceinline__ double obs_value(int id, const ObsCtx& c, int s, F h,
   }
 }
 
+// ---- generic scorers (eco_env_problems.hip; the table of F_i, quality and invalidity masks is at its top) ----
+// shared with the compact replay ring of eco_train.hip, which rebuilds observation rows with these statements
+__device__ __forceinline__ bool target_maximises(int t) {
+  return t == ECO_TARGET_MAX_IND_SET || t == ECO_TARGET_MAX_CLIQUE;
+}
+
+__device__ __forceinline__ int field_coef(int t, int w) {
+  switch (t) {
+    case ECO_TARGET_MIN_CUT: return -2 * w;
+    case ECO_TARGET_MIN_COVER: return w;
+    case ECO_TARGET_MIN_DOM_SET: return w > 0 ? -1 : 0;
+    default: return -w;
+  }
+}
+
+// per-vertex quality / invalidity masks (table above)
+__device__ __forceinline__ void vertex_masks(int t, int s, int F, int n1, int S0, int S1, int& qm, int& im) {
+  switch (t) {
+    case ECO_TARGET_MIN_COVER: qm = s; im = s * F; break;
+    case ECO_TARGET_MAX_IND_SET: qm = -s; im = -s * F; break;
+    case ECO_TARGET_MAX_CLIQUE: qm = -s; im = s > 0 ? 2 * (F - n1 + 1) : 2 * (n1 - F); break;
+    case ECO_TARGET_MIN_DOM_SET: {
+      const int alone = F == 0;
+      qm = s; im = s > 0 ? alone + S1 : -alone - S0;
+      break;
+    }
+    default: qm = -s * F; im = 0; break;  // MIN_CUT
+  }
+}
+
+// solution quality (score_solver.py:196-200 / :224-228) of a set of size n1: measure n1, lower bound 0,
+// quality normaliser N
+__device__ __forceinline__ int set_quality(int t, int n1, int N) { return target_maximises(t) ? n1 : N - n1; }
+
+// MinDomSet neighbour codes: bit0 = (x=0, P=0), bit1 = (x=0, P=1)
+__device__ __forceinline__ uint8_t mds_code(int s, int F) {
+  return s < 0 ? (uint8_t)((F == 0) | ((F == 1) << 1)) : (uint8_t)0;
+}
+
+// Episode quantities an observation row needs beyond the per-vertex masks.
+struct ProbObs {
+  double mlr, inorm, dist_best, hamming, nqi, nvi, term, ep_time, gvd, valid;
+  int basis;
+};
+
+__device__ __forceinline__ double prob_obs_value(int id, const ProbObs& c, int s, int qm, int im, int vm, int tsfk,
+                                                 const double* tab, bool cut_like) {
+  switch (id) {
+    case ECO_OBS_SPIN_STATE: return c.basis == ECO_BASIS_BINARY ? (double)(1 - s) / 2.0 : (double)s;
+    case ECO_OBS_IMMEDIATE_QUALITY_CHANGE:
+      // MIN_CUT: -(s * (J s)) in f64 (a zero product keeps its sign through the negation)
+      return (cut_like ? -((double)s * (double)(-qm * s)) : (double)qm) / c.mlr;
+    case ECO_OBS_IMMEDIATE_VALIDITY_DIFFERENCE: return (double)im / c.inorm;
+    case ECO_OBS_IMMEDIATE_VALIDITY_CHANGE: return vm ? 1.0 : 0.0;
+    case ECO_OBS_TIME_SINCE_FLIP: return tab[tsfk];
+    case ECO_OBS_EPISODE_TIME: return c.ep_time;
+    case ECO_OBS_TERMINATION_IMMANENCY: return c.term;
+    case ECO_OBS_NUMBER_OF_QUALITY_IMPROVEMENTS: return c.nqi;
+    case ECO_OBS_NUMBER_OF_VALIDITY_IMPROVEMENTS: return c.nvi;
+    case ECO_OBS_DISTANCE_FROM_BEST_SOLUTION: return c.dist_best;
+    case ECO_OBS_DISTANCE_FROM_BEST_STATE: return c.hamming;
+    case ECO_OBS_GLOBAL_VALIDITY_DIFFERENCE: return c.gvd;
+    default: return c.valid;  // ECO_OBS_VALIDITY_BIT
+  }
+}
+
 // LDS written by a wave and read back by the same wave only: a wave-scope fence suffices
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -31,7 +31,7 @@ def obs_x_stride(n_obs):
 ECO_MAX_SPINS = 2048          # wave-per-episode env kernels, eco_mpnn_forward, training, float weights, generic scorers
 ECO_MAX_SPINS_WG = 8192       # workgroup-per-episode env kernels and eco_mpnn_forward_wg: CUT, integer weights, inference
 MPNN_MAX_SPINS = 512          # saved-activation training (eco_mpnn_backward) up to here; eco_mpnn_grad_large above
-ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS)
+ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS); generic scorers: ECO_MAX_SPINS
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
 ECO_GRAPH_ER, ECO_GRAPH_BA, ECO_GRAPH_REGULAR, ECO_GRAPH_WS = 1, 2, 3, 4
 ECO_REGULAR_MAX_RESTARTS = 256   # restarts of the pairing algorithm per regular graph before ECO_ERR_GRAPH
@@ -136,6 +136,7 @@ _SIG = {
     "eco_replay_sample": (ctypes.c_int, [ctypes.POINTER(Replay), _I, _I, ctypes.c_uint64, ctypes.c_uint64, _P, _P,
                                          _P, _P, _P, _P, _P]),
     "eco_replay_compact_bytes": (ctypes.c_size_t, [_I, _I, _I]),
+    "eco_replay_compact_bytes_cfg": (ctypes.c_size_t, [ctypes.POINTER(EnvConfig), _I, _I]),
     "eco_replay_compact_snapshot": (ctypes.c_int, [ctypes.POINTER(EnvConfig), _P, _I, _P, _I, ctypes.c_int64, _P,
                                                    _P]),
     "eco_replay_compact_push": (ctypes.c_int, [ctypes.POINTER(EnvConfig), _P, _I, _P, _I, ctypes.c_int64, _P, _P, _P,

@@ -142,12 +142,18 @@ class DQN:
         self.M = int(train_minibatch or minibatch_size)
         # compact replay (one integer env state per transition, 4 B per vertex) for MaxCut envs on +-1
         # graphs; else fp32 features (always for a float-weighted store: the ring's local field is an int16)
-        eligible = (envs.cfg.optimisation_target == _lib.ECO_TARGET_CUT and envs.graphs.unit_weights
-                    and not envs.graphs.float_weights and envs.max_steps < 32768 and self.N <= _lib.ECO_COMPACT_MAX_SPINS)
+        # The set-problem targets take the compact ring (N <= ECO_MAX_SPINS) only on request: None keeps their
+        # feature ring, so no existing run changes its ring.
+        target = envs.cfg.optimisation_target
+        set_problem = _lib.ECO_TARGET_MIN_COVER <= target <= _lib.ECO_TARGET_MIN_DOM_SET
+        fits = (envs.graphs.unit_weights and not envs.graphs.float_weights and envs.max_steps < 32768)
+        eligible = fits and target == _lib.ECO_TARGET_CUT and self.N <= _lib.ECO_COMPACT_MAX_SPINS
+        allowed = eligible or (fits and set_problem and self.N <= _lib.ECO_MAX_SPINS)
         self.compact_replay = eligible if compact_replay is None else bool(compact_replay)
-        if self.compact_replay and not eligible:
-            raise ValueError("compact replay needs OptimisationTarget.CUT, +-1 (integer) weights, max_steps < 32768 and "
-                             f"n_spins <= {_lib.ECO_COMPACT_MAX_SPINS}")
+        if self.compact_replay and not allowed:
+            raise ValueError("compact replay needs +-1 (integer) weights, max_steps < 32768 and OptimisationTarget.CUT "
+                             f"with n_spins <= {_lib.ECO_COMPACT_MAX_SPINS}, or MIN_COVER / MIN_CUT / MAX_IND_SET / "
+                             f"MAX_CLIQUE / MIN_DOM_SET with n_spins <= {_lib.ECO_MAX_SPINS}")
         if self.compact_replay:
             self.replay_buffer = CompactReplayBuffer(replay_buffer_size, envs, seed=self.seed)
         else:

@@ -100,7 +100,11 @@ class CompactReplayBuffer:
     (4N + 80 B per transition, 880 B at N=200, against 64N B of fp32 feature rows for s and s').  s' is
     rebuilt from s, the action and the graph on sample, and both feature rows bit-exactly; sample() returns
     the same tuple as ReplayBuffer.sample.  Driven by the env: snapshot() after every reset, add_step()
-    after every step."""
+    after every step.
+
+    The set-problem envs (MIN_COVER, MIN_CUT, MAX_IND_SET, MAX_CLIQUE, MIN_DOM_SET; integer weights, N <= 2048)
+    use the same ring with their integer neighbour sum per vertex and six scalars per state: 4N + 112 B per
+    transition against the 128N B of their 16-float feature rows.  The library selects the layout from env.cfg."""
 
     def __init__(self, capacity, env, seed=0):
         self.env = env
@@ -110,9 +114,9 @@ class CompactReplayBuffer:
         self.device = env.graphs.device
         if env.n_envs > self._capacity:
             raise ValueError("compact replay: capacity must hold at least one batch of transitions")
-        nbytes = _lib.lib.eco_replay_compact_bytes(self.n_spins, self._capacity, env.n_envs)
+        nbytes = _lib.lib.eco_replay_compact_bytes_cfg(ctypes.byref(env.cfg), self._capacity, env.n_envs)
         if nbytes == 0:
-            raise ValueError("bad compact replay size")
+            raise ValueError(_lib.last_error() or "bad compact replay size")
         self.ring = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self._pushed = 0  # transitions added over the buffer's life (the k-th lives in slot k % (capacity + B))
         self._size = 0

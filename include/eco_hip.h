@@ -515,9 +515,22 @@ int eco_replay_sample(const eco_replay *rb, int32_t size, int32_t m, uint64_t se
  * over the buffer's life (the k-th lives in slot k % (capacity + batch)); push writes each episode's s'
  * straight into the slot of its next transition, so `ring` (caller-owned device memory of
  * eco_replay_compact_bytes()) has `batch` slots more than `capacity`.  Requires |J s| < 2^15 (reported
- * through eco_check_errors), max_steps < 2^15 and n_spins <= ECO_COMPACT_MAX_SPINS. */
+ * through eco_check_errors), max_steps < 2^15 and n_spins <= ECO_COMPACT_MAX_SPINS.
+ *
+ * The five generic-scorer targets (MIN_COVER, MIN_CUT, MAX_IND_SET, MAX_CLIQUE, MIN_DOM_SET) use the same calls and
+ * the same ring with their integer neighbour sum F_v in place of the local field and SIX float64 scalars per state
+ * (step, distance from the best solution, Hamming distance, global validity difference, invalidity normaliser, max
+ * local reward): 4N + 112 bytes per transition against 128N of 16-float feature rows.  Set size, invalidity degree,
+ * validity bit, the per-vertex masks and the improvement counts are rebuilt on sample from the row and the graph
+ * (MIN_DOM_SET: one more pass over the CSR rows), bit-exactly.  They take n_spins <= ECO_MAX_SPINS and |F_v| < 2^15;
+ * `ring` is then sized by eco_replay_compact_bytes_cfg().  The calls select by cfg->optimisation_target; any other
+ * target is ECO_ERR_TARGET.  Rejected with ECO_ERR_ARG and a message before any launch, for every target: a
+ * float-weighted config or graph set, max_steps > 32767, n_spins above the target's limit. */
 #define ECO_COMPACT_MAX_SPINS 8192
 size_t eco_replay_compact_bytes(int32_t n_spins, int32_t capacity, int32_t batch);
+/* Ring bytes for the env config: eco_replay_compact_bytes() for OptimisationTarget.CUT, the six-scalar layout for the
+ * generic-scorer targets, 0 (message in eco_last_error) for a config the ring rejects. */
+size_t eco_replay_compact_bytes_cfg(const eco_env_config *cfg, int32_t capacity, int32_t batch);
 /* After env reset (all episodes, or those with mask != 0): record their states as the s of the transitions
  * pushed + e. */
 int eco_replay_compact_snapshot(const eco_env_config *cfg, const void *env_state, int32_t batch, void *ring,
