@@ -208,7 +208,8 @@ class SetScorer(Scorer):
         s = np.asarray(s, dtype=np.float64)
         x = (s == 1).astype(np.float64)
         if self.target == MIN_COVER:
-            return s * (J @ (1.0 - x))
+            # s_i U_i in the reference's own operations (:308), which also fixes the sign of its zeros
+            return -1 * s * ((J * np.array(s == -1, dtype=np.float64)) @ s)
         if self.target == MAX_IND_SET:
             return -s * (J @ x)
         if self.target == MAX_CLIQUE:
@@ -225,7 +226,8 @@ class SetScorer(Scorer):
         c0 = (out & (P == 0)).astype(np.float64)
         c1 = (out & (P == 1)).astype(np.float64)
         alone = (P == 0).astype(np.float64)
-        return np.where(x == 1, alone + Jp @ c1, -alone - Jp @ c0)
+        # + 0.0: the reference subtracts integer counts (:699-700), so its zeros are +0.0
+        return np.where(x == 1, alone + Jp @ c1, -alone - Jp @ c0) + 0.0
 
 
 def make_scorer(target):
