@@ -184,5 +184,10 @@ GradLargeLayout mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t sl
 int mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
                            int32_t batch, const float* obs_x, const float* dq, void* workspace,
                            const GradLargeLayout& L, hipStream_t st);
+// eco_mpnn_grad_wg (2048 < N <= ECO_MAX_SPINS_WG, integer weights): the same workspace parts and launch sequence
+GradLargeLayout mpnn_grad_wg_layout(int32_t n_spins, int32_t batch, size_t slab_bytes);
+int mpnn_grad_wg_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
+                        int32_t batch, const float* obs_x, const float* dq, void* workspace,
+                        const GradLargeLayout& L, hipStream_t st);
 
 }  // namespace eco

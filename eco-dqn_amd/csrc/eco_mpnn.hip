@@ -1136,9 +1136,12 @@ __global__ __launch_bounds__(1024) void call_maxdeg_kernel(const eco_graph_set g
 // dh lives in the GR_DH rows instead of per-tile registers.  The Linears are the bf16x3 transposed fragments from
 // L2 (the WLDS = false branch).  No atomics: every reduction runs in a fixed order.
 // LDS: DQ [rows_pad] | DMEAN [64] | RED [NW][64]
-template <int NW, bool FW = false>
+// DQCAP: the capacity of DQ, rows_pad at the largest N of the entry that launches the instance (eco_mpnn_grad_large:
+// 2048; eco_mpnn_grad_wg: ECO_MAX_SPINS_WG, 32 KB more static LDS under the same one-workgroup-per-CU bound).
+template <int NW, bool FW = false, int DQCAP = MPNN_MAX_SPINS_LARGE>
 __global__ __launch_bounds__(64 * NW, 1) void mpnn_backward_large_kernel(MpnnArgs a, float* gbuf) {
-  __shared__ float DQ[MPNN_MAX_SPINS_LARGE];
+  static_assert(DQCAP % 16 == 0, "DQ holds rows_pad entries");
+  __shared__ float DQ[DQCAP];
   __shared__ float DMEAN[64];
   __shared__ float RED[NW * 64];
   constexpr int NT = 64 * NW;
@@ -1838,9 +1841,8 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
 // tensors + per-graph partials (mpnn_grad_ws_bytes), one [rows_pad][64] gather-source buffer per episode, the
 // forward's three ping-pong row buffers, the weight-gradient slabs; every part 256 B aligned.  total = 0: no such
 // call (N outside (512, 2048], batch < 1 or batch * n_spins rows beyond the 32-bit row index of the weight gradients).
-GradLargeLayout eco::mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
+static GradLargeLayout grad_rows_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
   GradLargeLayout L{};
-  if (n_spins <= MPNN_MAX_SPINS || n_spins > MPNN_MAX_SPINS_LARGE || batch < 1) return L;
   const size_t RT = (size_t)n_spins * batch;
   if (RT > (size_t)INT32_MAX / 64) return L;
   const size_t rows_pad = ((size_t)n_spins + 15) & ~(size_t)15;
@@ -1851,6 +1853,17 @@ GradLargeLayout eco::mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size
   L.slabs = L.hbuf + (size_t)batch * rows_pad * 64 * 3 * sizeof(float);
   L.total = L.slabs + slab_bytes;
   return L;
+}
+
+GradLargeLayout eco::mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
+  if (n_spins <= MPNN_MAX_SPINS || n_spins > MPNN_MAX_SPINS_LARGE || batch < 1) return GradLargeLayout{};
+  return grad_rows_layout(n_spins, batch, slab_bytes);
+}
+
+// eco_mpnn_grad_wg's workspace: the same parts in the same order for 2048 < N <= ECO_MAX_SPINS_WG
+GradLargeLayout eco::mpnn_grad_wg_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
+  if (!forward_wg_range(n_spins) || batch < 1) return GradLargeLayout{};
+  return grad_rows_layout(n_spins, batch, slab_bytes);
 }
 
 // The launches of eco_mpnn_grad_large before the weight-gradient tail: the call's max degree, the saving forward,
@@ -1882,6 +1895,35 @@ int eco::mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco
     mpnn_backward_large_kernel<8, false><<<a.B, 512, 0, st>>>(a, gbuf);
   }
   return check_launch("mpnn_grad_large");
+}
+
+// The launches of eco_mpnn_grad_wg before the weight-gradient tail: eco_mpnn_grad_large's sequence on the integer-
+// weight instances, the backward with a DQ of ECO_MAX_SPINS_WG entries.  The kernels walk an episode's rows in loops
+// bounded by N and index across episodes in size_t (DESIGN section 25 has the audit); graphs_per_block is 1 by
+// construction.  The caller has checked the pointers, the range and the layout.
+int eco::mpnn_grad_wg_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
+                             int32_t batch, const float* obs_x, const float* dq, void* workspace,
+                             const GradLargeLayout& L, hipStream_t st) {
+  if (!L.total || !forward_wg_range(gs->n_spins) || gs->edge_weights)
+    return fail(ECO_ERR_ARG, "eco_mpnn_grad_wg takes 2048 < N <= 8192 with integer weights");
+  MpnnArgs a{};
+  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = gs->n_spins; a.gpb = 1;
+  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = ECO_NORM_PER_CALL;
+  a.err = err_word();
+  char* ws = (char*)workspace;
+  a.call_maxdeg = (int*)ws;
+  a.sv = (float*)(ws + L.sv);
+  a.gr = (float*)(ws + L.gr);
+  a.dq = dq;
+  float* gbuf = (float*)(ws + L.g);
+  float* hbuf = (float*)(ws + L.hbuf);
+  call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)ws);
+  const int rows_pad = (a.N + 15) & ~15;
+  const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
+  if (a.xw == 16) launch_lds(mpnn_forward_large_kernel<8, false, 16, true>, a.B, 512, lds, st, a, hbuf);
+  else launch_lds(mpnn_forward_large_kernel<8, false, 8, true>, a.B, 512, lds, st, a, hbuf);
+  mpnn_backward_large_kernel<8, false, ECO_MAX_SPINS_WG><<<a.B, 512, 0, st>>>(a, gbuf);
+  return check_launch("mpnn_grad_wg");
 }
 
 // ---- split2_pk hazard probe (the v_fma_mix inline asm carries its own wait states) ----

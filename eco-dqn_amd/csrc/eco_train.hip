@@ -1105,6 +1105,43 @@ extern "C" int eco_mpnn_grad_large(const float* packed, int32_t n_obs_in, const 
                     (float*)(ws + L.slabs), grad, st);
 }
 
+// The gradient above eco_mpnn_grad_large's range: the same launch sequence and workspace parts on integer-weighted
+// sets of 2048 < N <= ECO_MAX_SPINS_WG vertices (mpnn_grad_wg_launch).  batch * n_spins keeps the 32-bit row index of
+// the weight-gradient jobs: at most (2^31 - 1) / 64 rows, 4095 samples of 8192 vertices.
+static const char* kGradWgRange = "eco_mpnn_grad_wg takes 2048 < N <= 8192";
+
+extern "C" size_t eco_mpnn_grad_wg_workspace_bytes(int32_t n_spins, int32_t batch) {
+  return mpnn_grad_wg_layout(n_spins, batch, slab_bytes()).total;
+}
+
+extern "C" int eco_mpnn_grad_wg(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                                const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
+                                float* grad, void* workspace, eco_stream_t stream) {
+  if (!packed || !gs || !graph_ids || !obs_x || !dq || !grad || !workspace)
+    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": null argument");
+  if (!gs->row_ptr || !gs->edge_base || !gs->edges || !gs->deg || !gs->max_deg)
+    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": incomplete graph set");
+  const int N = gs->n_spins;
+  if (N <= ECO_MAX_SPINS || N > ECO_MAX_SPINS_WG)
+    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + " (got N = " + std::to_string(N) +
+                                 "); eco_mpnn_grad_large is the gradient for 512 < N <= 2048");
+  if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return fail(ECO_ERR_ARG, "n_obs_in out of range [1, 16]");
+  if (batch < 1) return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": batch must be >= 1");
+  if (gs->n_graphs < 1) return fail(ECO_ERR_ARG, "empty graph set");
+  if (gs->edge_weights)
+    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + " with integer weights only (float-weighted sets train up "
+                                                         "to 2048 vertices)");
+  const GradLargeLayout L = mpnn_grad_wg_layout(N, batch, slab_bytes());
+  if (!L.total)
+    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": batch * n_spins beyond the 32-bit row index ((2^31 - 1) / 64)");
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = mpnn_grad_wg_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, workspace, L, st))
+    return rc;
+  char* ws = (char*)workspace;
+  return wgrad_tail((const float*)(ws + L.sv), (const float*)(ws + L.gr), n_obs_in, N, batch, batch, obs_x,
+                    (float*)(ws + L.slabs), grad, st);
+}
+
 extern "C" int eco_dqn_td_weighted(const float* q_s, const float* q_target_next, const int32_t* a_star,
                                    const int32_t* actions, const float* rewards, const float* dones, int32_t batch,
                                    int32_t n_spins, float gamma, int32_t clip_q_targets, int32_t loss_kind, float* dq,

@@ -29,7 +29,7 @@ def obs_x_stride(n_obs):
     """ECO_OBS_X_STRIDE: floats per node-feature row of obs_x."""
     return 8 if n_obs <= 8 else 16
 ECO_MAX_SPINS = 2048          # wave-per-episode env kernels, eco_mpnn_forward, training, float weights, generic scorers
-ECO_MAX_SPINS_WG = 8192       # workgroup-per-episode env kernels and eco_mpnn_forward_wg: CUT, integer weights, inference
+ECO_MAX_SPINS_WG = 8192       # workgroup-per-episode env kernels and eco_mpnn_forward_wg / eco_mpnn_grad_wg: CUT, integer weights
 MPNN_MAX_SPINS = 512          # saved-activation training (eco_mpnn_backward) up to here; eco_mpnn_grad_large above
 ECO_COMPACT_MAX_SPINS = 8192  # include/eco_hip.h: compact replay (sample rebuilds s' in LDS); generic scorers: ECO_MAX_SPINS
 ECO_NORM_PER_GRAPH, ECO_NORM_PER_CALL, ECO_NORM_PER_CALL_REUSE = 0, 1, 2
@@ -125,6 +125,8 @@ _SIG = {
     "eco_mpnn_backward": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P, _P, _P]),
     "eco_mpnn_grad_large_workspace_bytes": (ctypes.c_size_t, [_I, _I]),
     "eco_mpnn_grad_large": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P, _P]),
+    "eco_mpnn_grad_wg_workspace_bytes": (ctypes.c_size_t, [_I, _I]),
+    "eco_mpnn_grad_wg": (ctypes.c_int, [_P, _I, ctypes.POINTER(GraphSet), _P, _I, _P, _P, _P, _P, _P]),
     "eco_dqn_td": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _P, _P, _P, _P]),
     "eco_dqn_td_loss": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P]),
     "eco_dqn_td_weighted": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P, _P,

@@ -10,7 +10,8 @@ advances B episodes.  Everything on the step path runs in libecohip:
   train     -> online(s') argmax, target(s') gather, online(s) forward with saved
                activations, TD + MSE / Huber gradient, MPNN backward, optional gradient-norm clipping,
                Adam (dqn.py:403-451); above 512 vertices online(s) is an inference forward and the
-               gradient one self-contained call that recomputes it (MPNN.grad_large)
+               gradient one self-contained call that recomputes it (MPNN.grad_large; MPNN.grad_wg for 2049 to
+               8192 vertices with train_large_graphs=True)
 Schedules are per env-step as in the reference; a vector step advances the
 counter by B.  The replay ratio of the reference (minibatch_size/update_frequency
 samples per env-step, 64/32 = 2 in train_eco.py:136-137) is kept by running
@@ -51,7 +52,8 @@ class DQN:
                  network_save_path='network', evaluate=True, test_envs=None, test_episodes=20,
                  test_frequency=10000, test_save_path='test_scores', test_metric=TestMetric.ENERGY_ERROR,
                  logging=True, seed=None, train_minibatch=None, graph_pool_ids=None, regenerate_graphs=None,
-                 compact_replay=None, target_sync="grad_steps", overlap_evaluation=True, prioritised_replay=None):
+                 compact_replay=None, target_sync="grad_steps", overlap_evaluation=True, prioritised_replay=None,
+                 train_large_graphs=False):
         if isinstance(envs, (list, tuple)):
             if len(envs) != 1:
                 raise NotImplementedError("pass one VecSpinSystem (it already holds B episodes)")
@@ -67,11 +69,17 @@ class DQN:
                 raise ValueError("max_grad_norm must be None or a finite positive number")
             max_grad_norm = float(max_grad_norm)
         if envs.graphs.n_spins > _lib.ECO_MAX_SPINS:
-            # the gradient (eco_mpnn_grad_large) and the training forwards stop at ECO_MAX_SPINS; above it the env and
-            # the network run inference and search only (solvers, test_network)
-            raise ValueError(f"DQN trains on graphs of at most ECO_MAX_SPINS={_lib.ECO_MAX_SPINS} vertices, got N = "
-                             f"{envs.graphs.n_spins}: {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} is inference "
-                             "and search only")
+            # eco_mpnn_grad_large and eco_mpnn_forward_pair stop at ECO_MAX_SPINS.  train_large_graphs=True opts in to
+            # the gradient of 2049 to ECO_MAX_SPINS_WG vertices (MPNN.grad_wg; MaxCut on integer weights, which is
+            # what the env and the store take there); the default keeps such a store to inference and search
+            if not train_large_graphs:
+                raise ValueError(f"DQN trains on graphs of at most ECO_MAX_SPINS={_lib.ECO_MAX_SPINS} vertices, got N "
+                                 f"= {envs.graphs.n_spins}: {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} is "
+                                 "inference and search only unless train_large_graphs=True is passed")
+            if regenerate_graphs is not None:
+                raise ValueError(f"regenerate_graphs takes graphs of at most ECO_MAX_SPINS={_lib.ECO_MAX_SPINS} "
+                                 f"vertices (the device generators are not run above it), got N = "
+                                 f"{envs.graphs.n_spins}: train on a fixed pool there")
         self.loss = loss
         self._loss_kind = _lib.ECO_LOSS_HUBER if loss == "huber" else _lib.ECO_LOSS_MSE
         self.max_grad_norm = max_grad_norm
@@ -230,6 +238,11 @@ class DQN:
     # ---------------------------------------------------------------- buffers
     def _alloc_train_buffers(self, m):
         dev = self.device
+        self._wg = self.N > _lib.ECO_MAX_SPINS   # 2049 to ECO_MAX_SPINS_WG vertices: MPNN.grad_wg, no pair forward
+        if self._wg and self.network.grad_wg_bytes(self.N, m) == 0:   # before anything is reallocated
+            raise ValueError(f"train_minibatch = {m} samples of N = {self.N} vertices exceed the gradient's row "
+                             f"index: train_minibatch * N must be at most (2^31 - 1) / 64 = {(2 ** 31 - 1) // 64} "
+                             f"(train_minibatch <= {(2 ** 31 - 1) // 64 // self.N})")
         self.q_s = torch.empty(m, self.N, device=dev)
         self.q_tn = torch.empty(m, self.N, device=dev)
         self.a_star = torch.empty(m, dtype=torch.int32, device=dev)
@@ -241,7 +254,10 @@ class DQN:
         # above 512 vertices the gradient is one self-contained call (MPNN.grad_large) with one workspace; there is
         # no saved-activation buffer between a forward and a backward
         self._large = self.N > _lib.MPNN_MAX_SPINS
-        if self._large:
+        if self._wg:
+            self.saved = self.bw_ws = None
+            self.grad_ws = torch.empty(self.network.grad_wg_bytes(self.N, m), dtype=torch.uint8, device=dev)
+        elif self._large:
             self.saved = self.bw_ws = None
             self.grad_ws = torch.empty(self.network.grad_large_bytes(self.N, m), dtype=torch.uint8, device=dev)
         else:
@@ -310,7 +326,14 @@ class DQN:
             self._alloc_train_buffers(m)
         net, tgt = self.network, self.target_network
         greedy = _lib.ActConfig(0.0, int(self.acting_in_reversible_spin_env), float(self.allowed_value), 0, 0)
-        if self.double_dqn:
+        if self.double_dqn and self._wg:
+            # eco_mpnn_forward_pair stops at ECO_MAX_SPINS: the pair is two forwards.  The online one runs second, so
+            # the per-call max degree Q(s) reuses below is the one it left in its own workspace
+            tgt.forward_graphs(xn, self.graphs, gid, norm_scope=_lib.ECO_NORM_PER_CALL, q_out=self.q_tn)
+            net.forward_graphs(xn, self.graphs, gid, norm_scope=_lib.ECO_NORM_PER_CALL, act=greedy,
+                               actions_out=self.a_star)
+            scope_s = _lib.ECO_NORM_PER_CALL_REUSE
+        elif self.double_dqn:
             # greedy_actions = network(s').argmax (masked for irreversible envs), q_t = target(s')[a*]
             net.forward_pair_graphs(tgt, xn, self.graphs, gid, norm_scope=_lib.ECO_NORM_PER_CALL, act=greedy,
                                     actions_out=self.a_star, q_out_other=self.q_tn)
@@ -342,7 +365,9 @@ class DQN:
                                                     _lib.ptr(loss_dev), _lib.ptr(w), _lib.ptr(self.abs_td),
                                                     _lib.stream_ptr()))
             self._prio.update(self.abs_td)
-        if self._large:
+        if self._wg:
+            net.grad_wg(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
+        elif self._large:
             net.grad_large(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
         else:
             net.backward_graphs(xs, self.graphs, gid, self.saved, self.dq, self.grad, workspace=self.bw_ws)

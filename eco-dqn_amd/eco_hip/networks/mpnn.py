@@ -236,6 +236,37 @@ class MPNN(torch.nn.Module):
             self.timer.append((ev[0], ev[1], -B, graph_ids))   # negative batch marks a backward launch
         return grad_out
 
+    @staticmethod
+    def grad_wg_bytes(n_spins, batch):
+        """Workspace bytes of grad_wg (0: not a size it takes)."""
+        return _lib.lib.eco_mpnn_grad_wg_workspace_bytes(n_spins, batch)
+
+    def grad_wg(self, obs_x, graphs, graph_ids, dq, grad_out, workspace=None, stream=None):
+        """grad_large for 2048 < N <= 8192 (eco_mpnn_grad_wg): the same self-contained gradient under
+        norm_scope=ECO_NORM_PER_CALL, on integer-weighted graphs.  The workspace is about 27 x rows_pad x 256 B per
+        sample (56.6 MB at 8192 vertices)."""
+        B, N = obs_x.shape[0], obs_x.shape[1]
+        self._check_x(obs_x)
+        self._ensure_packed(stream)
+        need = self.grad_wg_bytes(N, B)
+        if need == 0:
+            raise ValueError(f"grad_wg takes {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} and batch * N <= "
+                             f"(2^31 - 1) / 64 (got N = {N}, batch = {B}); grad_large is the gradient for 512 < N <= "
+                             f"{_lib.ECO_MAX_SPINS}")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=obs_x.device)
+        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
+        if self.timer is not None:
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            ev[0].record()
+        _lib.check(_lib.lib.eco_mpnn_grad_wg(
+            _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
+            _lib.ptr(obs_x), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace), _lib.stream_ptr(stream)))
+        if self.timer is not None:
+            ev[1].record()
+            self.timer.append((ev[0], ev[1], -B, graph_ids))   # negative batch marks a backward launch
+        return grad_out
+
     # ---- reference-format forward (drop-in for mpnn.py:40-77) ----
     def forward(self, obs):
         """obs [B, n_obs_in+N, N] or [n_obs_in+N, N] -> Q [B, N] (squeezed like mpnn.py:75).

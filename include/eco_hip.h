@@ -427,6 +427,22 @@ int eco_mpnn_grad_large(const float *packed, int32_t n_obs_in, const eco_graph_s
                         int32_t batch, const float *obs_x, const float *dq, float *grad, void *workspace,
                         eco_stream_t stream);
 
+/* Training above 2048 vertices: eco_mpnn_grad_large's gradient for ECO_MAX_SPINS < N <= ECO_MAX_SPINS_WG (2049 to
+ * 8192), in ONE self-contained call with the same arguments and the same meaning: grad[flat, state_dict order] =
+ * d(sum dq . Q)/dparams under norm scope ECO_NORM_PER_CALL, the forward recomputed inside the call on per-episode
+ * global-memory rows (one workgroup per episode).  Q(s) for the TD error comes from eco_mpnn_forward_wg.  Integer
+ * weights only (a float-weighted set, gs->edge_weights, is ECO_ERR_ARG, as in eco_mpnn_forward_wg); 8- and 16-float
+ * observation rows.  grad is overwritten; no atomics, every reduction in a fixed order: two calls give the same bytes.
+ * workspace: eco_mpnn_grad_wg_workspace_bytes(n_spins, batch) bytes, all scratch, in eco_mpnn_grad_large's layout:
+ * about 27 x rows_pad x 256 B per sample (56.6 MB at 8192) plus the weight-gradient slabs.
+ * The query returns 0 outside 2048 < n_spins <= 8192, for batch < 1 and when batch * n_spins exceeds (2^31 - 1) / 64
+ * (the 32-bit row index of the weight-gradient jobs: at most 4095 samples of 8192 vertices).  ECO_ERR_ARG before any
+ * launch, with a message naming "2048 < N <= 8192": such a size, a NULL pointer, a float-weighted set. */
+size_t eco_mpnn_grad_wg_workspace_bytes(int32_t n_spins, int32_t batch);
+int eco_mpnn_grad_wg(const float *packed, int32_t n_obs_in, const eco_graph_set *gs, const int32_t *graph_ids,
+                     int32_t batch, const float *obs_x, const float *dq, float *grad, void *workspace,
+                     eco_stream_t stream);
+
 /* Double-DQN TD target and MSE gradient (dqn.py:409-440, reversible env):
  * q_t = q_target_next[b][a_star[b]] (a_star = argmax of the online net on s'),
  * td = r + (1 - done) * gamma * q_t; loss = mean((q_s[b][a_b] - td)^2);
