@@ -175,19 +175,40 @@ int mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_graph_
                          int32_t batch, const float* obs_x, const void* saved, const float* dq, void* gradws,
                          hipStream_t st);
 
-// eco_mpnn_grad_large (512 < N <= 2048): byte offsets of the parts of its workspace, and the launches that fill
-// the saved activations and the gradient workspace inside it (eco_train.hip adds the weight-gradient tail)
-struct GradLargeLayout {
-  size_t sv, gr, g, hbuf, slabs, total;  // total = 0: unsupported size
+// ---- the global-row entries: one workgroup per episode, the episode's rows in global memory ----
+// A range of N served by mpnn_forward_large_kernel / mpnn_backward_large_kernel.  The two ranges share every line of
+// host code; what differs between them is in this descriptor.
+struct RowsRange {
+  const char* name;    // the range's entries are eco_mpnn_grad_<name> and, above eco_mpnn_forward's range, eco_mpnn_forward_<name>
+  int lo, hi;          // lo < N <= hi
+  bool float_weights;  // float-weighted graph sets accepted
+  int dqcap;           // DQCAP of the backward instance: rows_pad at hi
 };
-GradLargeLayout mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes);
-int mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
-                           int32_t batch, const float* obs_x, const float* dq, void* workspace,
-                           const GradLargeLayout& L, hipStream_t st);
-// eco_mpnn_grad_wg (2048 < N <= ECO_MAX_SPINS_WG, integer weights): the same workspace parts and launch sequence
-GradLargeLayout mpnn_grad_wg_layout(int32_t n_spins, int32_t batch, size_t slab_bytes);
-int mpnn_grad_wg_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
-                        int32_t batch, const float* obs_x, const float* dq, void* workspace,
-                        const GradLargeLayout& L, hipStream_t st);
+constexpr RowsRange kRowsLarge = {"large", MPNN_MAX_SPINS, MPNN_MAX_SPINS_LARGE, true, MPNN_MAX_SPINS_LARGE};
+constexpr RowsRange kRowsWg = {"wg", MPNN_MAX_SPINS_LARGE, ECO_MAX_SPINS_WG, false, ECO_MAX_SPINS_WG};
+inline bool rows_in_range(const RowsRange& r, int n_spins) { return n_spins > r.lo && n_spins <= r.hi; }
+// "eco_mpnn_<kind>_<name> takes <lo> < N <= <hi>: <reason>" (kind: "grad" or "forward")
+inline std::string rows_message(const RowsRange& r, const char* kind, const std::string& reason) {
+  return std::string("eco_mpnn_") + kind + "_" + r.name + " takes " + std::to_string(r.lo) + " < N <= " +
+         std::to_string(r.hi) + ": " + reason;
+}
+// What every entry of a range checks of its graph set and sizes before anything is launched (the caller has checked
+// its pointers): a complete, non-empty set of lo < N <= hi vertices, n_obs_in, batch >= 1, the range's weights.
+int mpnn_rows_check(const RowsRange& r, const char* kind, const eco_graph_set* gs, int32_t n_obs_in, int32_t batch);
+// an episode's rows padded to whole 16-row tiles, and the bytes of `count` [rows_pad][64] f32 row buffers per episode
+inline size_t padded_rows(int32_t n_spins) { return ((size_t)n_spins + 15) & ~(size_t)15; }
+inline size_t rows_buffer_bytes(int32_t n_spins, int32_t batch, int count) {
+  return (size_t)batch * padded_rows(n_spins) * 64 * count * sizeof(float);
+}
+
+// eco_mpnn_grad_<name>: byte offsets of the parts of its workspace (total = 0: no such call), and the launches that
+// fill the saved activations and the gradient workspace inside it (eco_train.hip adds the weight-gradient tail)
+struct GradRowsLayout {
+  size_t sv, gr, g, hbuf, slabs, total;
+};
+GradRowsLayout mpnn_grad_rows_layout(const RowsRange& r, int32_t n_spins, int32_t batch, size_t slab_bytes);
+int mpnn_grad_rows_launch(const RowsRange& r, const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                          const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
+                          void* workspace, const GradRowsLayout& L, hipStream_t st);
 
 }  // namespace eco

@@ -1428,23 +1428,32 @@ __global__ __launch_bounds__(64 * NW, 1) void mpnn_backward_large_kernel(MpnnArg
   }
 }
 
+// The MpnnArgs fields every launch fills the same way; the rest stay zero for the caller.  graphs_per_block is 1 from
+// 208 vertices on, so on every global-row size.
+static void fill_args(MpnnArgs& a, const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                      const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope) {
+  a = MpnnArgs{};
+  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = gs->n_spins;
+  a.gpb = graphs_per_block(a.N, batch);
+  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
+  a.err = err_word();
+}
+
+// max_spins: MPNN_MAX_SPINS_LARGE but for eco_mpnn_forward_wg, which has checked its own range
 static int prepare(MpnnArgs& a, const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
-                   const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope) {
+                   const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope,
+                   int max_spins = MPNN_MAX_SPINS_LARGE) {
   if (!packed || !gs || !graph_ids || !obs_x) return fail(ECO_ERR_ARG, "null argument");
   if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return fail(ECO_ERR_ARG, "n_obs_in out of range [1, 16]");
   if (batch < 1) return fail(ECO_ERR_ARG, "batch must be >= 1");
-  const int N = gs->n_spins;
-  if (N < 1 || N > MPNN_MAX_SPINS_LARGE) return fail(ECO_ERR_ARG, "mpnn supports 1 <= N <= 2048");
+  if (gs->n_spins < 1 || gs->n_spins > max_spins) return fail(ECO_ERR_ARG, "mpnn supports 1 <= N <= 2048");
   if (norm_scope != ECO_NORM_PER_GRAPH && norm_scope != ECO_NORM_PER_CALL)
     return fail(ECO_ERR_ARG, "bad norm_scope");
   // a float-weighted set runs the CSR-gather kernels only: unit_weights == 0 keeps it off the dense, DL, shared-graph
   // and fused-pair kernels (dense_eligible, dl_eligible and the shared-graph test all need unit_weights)
   if (gs->edge_weights && gs->unit_weights)
     return fail(ECO_ERR_ARG, "graph set has float edge_weights and unit_weights set");
-  a = MpnnArgs{};
-  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = N; a.gpb = graphs_per_block(N, batch);
-  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
-  a.err = err_word();
+  fill_args(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope);
   return ECO_OK;
 }
 
@@ -1478,7 +1487,7 @@ extern "C" size_t eco_mpnn_workspace_bytes(int32_t n_spins, int32_t batch) {
   if (n_spins < 1 || batch < 1) return 0;
   if (n_spins > MPNN_MAX_SPINS) {  // + per episode Z/h ping-pong rows and e rows (mpnn_forward_large_kernel),
                                   // or the node-major buffers of the shared-graph path, whichever is larger
-    const size_t per_ep = (size_t)batch * ((n_spins + 15) & ~15) * 64 * 3 * sizeof(float);
+    const size_t per_ep = rows_buffer_bytes(n_spins, batch, 3);
     const size_t shared = shared_ws_bytes(n_spins, batch);
     return 256 + (per_ep > shared ? per_ep : shared);
   }
@@ -1642,19 +1651,22 @@ static int launch_csr(const MpnnArgs& a, bool backward, bool save, hipStream_t s
   return check_launch(backward ? "mpnn_backward" : "mpnn_forward");
 }
 
-// N > 512 inference on the per-episode global-memory kernel: 8 waves, {float weights} x {8-, 16-float rows}
-static int launch_large(const MpnnArgs& a, void* workspace, hipStream_t st) {
+// The per-episode global-memory forward, one workgroup of 8 waves per episode with its three row buffers in hbuf:
+// the instance of {float weights} x {8-, 16-float rows (more than 8 observables)} x {saving}.
+static void launch_forward_large(const MpnnArgs& a, float* hbuf, bool save, hipStream_t st) {
   const int rows_pad = (a.N + 15) & ~15;
   const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
-  float* hbuf = (float*)((char*)workspace + 256);
-  const bool wide = a.xw == 16;  // more than 8 observables: 16-float rows
-  if (a.gs.edge_weights) {
-    if (wide) launch_lds(mpnn_forward_large_kernel<8, true, 16>, a.B, 512, lds, st, a, hbuf);
-    else launch_lds(mpnn_forward_large_kernel<8, true, 8>, a.B, 512, lds, st, a, hbuf);
-  } else {
-    if (wide) launch_lds(mpnn_forward_large_kernel<8, false, 16>, a.B, 512, lds, st, a, hbuf);
-    else launch_lds(mpnn_forward_large_kernel<8, false, 8>, a.B, 512, lds, st, a, hbuf);
-  }
+  static void (*const table[2][2][2])(MpnnArgs, float*) = {
+      {{mpnn_forward_large_kernel<8, false, 8, false>, mpnn_forward_large_kernel<8, false, 8, true>},
+       {mpnn_forward_large_kernel<8, false, 16, false>, mpnn_forward_large_kernel<8, false, 16, true>}},
+      {{mpnn_forward_large_kernel<8, true, 8, false>, mpnn_forward_large_kernel<8, true, 8, true>},
+       {mpnn_forward_large_kernel<8, true, 16, false>, mpnn_forward_large_kernel<8, true, 16, true>}}};
+  launch_lds(table[a.gs.edge_weights != nullptr][a.xw == 16][save], a.B, 512, lds, st, a, hbuf);
+}
+
+// N > 512 inference: the non-saving forward on the row buffers after the workspace header
+static int launch_large(const MpnnArgs& a, void* workspace, hipStream_t st) {
+  launch_forward_large(a, (float*)((char*)workspace + 256), false, st);
   return check_launch("mpnn_forward_large");
 }
 
@@ -1666,16 +1678,19 @@ struct FwdHead {
   int32_t* actions;
 };
 
-// Per-call set-up of eco_mpnn_forward (n = 1) and eco_mpnn_forward_pair (n = 2): folds ECO_NORM_PER_CALL_REUSE (the
-// workspace already holds the call's max degree) into PER_CALL, validates, fills a[0 .. n) (which differ in P, q,
-// act and actions only) and routes the call.  Unless a pair call falls back to two single forwards (fused false:
-// nothing is launched, they do their own set-up), the call's norm.max() reduction is launched here.
+// Per-call set-up of eco_mpnn_forward, eco_mpnn_forward_wg (n = 1) and eco_mpnn_forward_pair (n = 2): folds
+// ECO_NORM_PER_CALL_REUSE (the workspace already holds the call's max degree) into PER_CALL, validates, fills
+// a[0 .. n) (which differ in P, q, act and actions only) and routes the call.  Unless a pair call falls back to two
+// single forwards (fused false: nothing is launched, they do their own set-up), the call's norm.max() reduction is
+// launched here.  wg: the call is eco_mpnn_forward_wg's, which has checked its range and runs ECO_ROUTE_LARGE alone.
 static int forward_setup(MpnnArgs* a, const FwdHead* h, int n, int32_t n_obs_in, const eco_graph_set* gs,
                          const int32_t* graph_ids, int32_t batch, const float* obs_x, int32_t norm_scope, void* saved,
-                         void* workspace, hipStream_t st, int& family, bool& fused) {
+                         void* workspace, hipStream_t st, int& family, bool& fused, bool wg = false) {
   const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;
   if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
-  if (const int rc = prepare(a[0], h[0].packed, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope)) return rc;
+  if (const int rc = prepare(a[0], h[0].packed, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope,
+                             wg ? kRowsWg.hi : MPNN_MAX_SPINS_LARGE))
+    return rc;
   if (!workspace) return fail(ECO_ERR_ARG, "null workspace");
   for (int i = 0; i < n; ++i)
     if (h[i].act && !h[i].actions) return fail(ECO_ERR_ARG, "act config without actions buffer");
@@ -1692,7 +1707,7 @@ static int forward_setup(MpnnArgs* a, const FwdHead* h, int n, int32_t n_obs_in,
     a[i].actions = h[i].actions;
   }
   const int paths = kernel_paths();
-  family = mpnn_route(a[0], paths, saved != nullptr);
+  family = wg ? ECO_ROUTE_LARGE : mpnn_route(a[0], paths, saved != nullptr);
   fused = n == 2 && pair_fused(a[0], family, paths);
   if (n == 2 && !fused) return ECO_OK;
   if (n == 1) a[0].act_skip = act_skips(a[0], family, paths, saved != nullptr);  // the pair kernels never skip
@@ -1759,14 +1774,27 @@ extern "C" int eco_mpnn_forward(const float* packed, int32_t n_obs_in, const eco
 // 2^19).  eco_mpnn_forward and eco_mpnn_route keep their range: this entry has its own workspace layout -- the
 // 256 B header (call max degree; the shared-graph key slot, zeroed by the kernel) and three [rows_pad][64] f32 row
 // buffers per episode -- and never takes the shared-graph path, whose tables are one LDS block.
-static bool forward_wg_range(int32_t n_spins) { return n_spins > MPNN_MAX_SPINS_LARGE && n_spins <= ECO_MAX_SPINS_WG; }
-static const char* kForwardWgRange = "eco_mpnn_forward_wg takes 2048 < N <= 8192";
+
+// What every entry of a global-row range asks of its graph set and sizes; what differs between the two ranges is in
+// the RowsRange descriptor (eco_mpnn.h).
+int eco::mpnn_rows_check(const RowsRange& r, const char* kind, const eco_graph_set* gs, int32_t n_obs_in,
+                         int32_t batch) {
+  auto no = [&](const std::string& reason) { return fail(ECO_ERR_ARG, rows_message(r, kind, reason)); };
+  if (!gs->row_ptr || !gs->edge_base || !gs->edges || !gs->deg || !gs->max_deg) return no("incomplete graph set");
+  if (!rows_in_range(r, gs->n_spins)) return no("got N = " + std::to_string(gs->n_spins));
+  if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return no("n_obs_in out of range [1, 16]");
+  if (batch < 1) return no("batch must be >= 1");
+  if (gs->n_graphs < 1) return no("empty graph set");
+  if (gs->edge_weights && !r.float_weights)
+    return no("integer weights only (float-weighted sets run up to " + std::to_string(kRowsLarge.hi) + " vertices)");
+  if (gs->edge_weights && gs->unit_weights) return no("graph set has float edge_weights and unit_weights set");
+  return ECO_OK;
+}
 
 extern "C" size_t eco_mpnn_forward_wg_workspace_bytes(int32_t n_spins, int32_t batch, int32_t n_obs_in) {
-  if (!forward_wg_range(n_spins) || batch < 1 || n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return 0;
-  const size_t rows_pad = ((size_t)n_spins + 15) & ~(size_t)15;
-  if ((size_t)batch * rows_pad > (size_t)INT32_MAX / 64) return 0;  // the 32-bit row index
-  return 256 + (size_t)batch * rows_pad * 64 * 3 * sizeof(float);
+  if (!rows_in_range(kRowsWg, n_spins) || batch < 1 || n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return 0;
+  if ((size_t)batch * padded_rows(n_spins) > (size_t)INT32_MAX / 64) return 0;  // the 32-bit row index
+  return 256 + rows_buffer_bytes(n_spins, batch, 3);
 }
 
 extern "C" int eco_mpnn_forward_wg(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
@@ -1774,39 +1802,19 @@ extern "C" int eco_mpnn_forward_wg(const float* packed, int32_t n_obs_in, const 
                                    float* q, const eco_act_config* act, int32_t* actions, void* workspace,
                                    eco_stream_t stream) {
   if (!packed || !gs || !graph_ids || !obs_x || !workspace)
-    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": null argument");
-  if (!gs->row_ptr || !gs->edge_base || !gs->edges || !gs->deg || !gs->max_deg)
-    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": incomplete graph set");
-  if (!forward_wg_range(gs->n_spins))
-    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + " (got N = " + std::to_string(gs->n_spins) +
-                                 "); eco_mpnn_forward is the forward up to 2048 vertices");
-  if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return fail(ECO_ERR_ARG, "n_obs_in out of range [1, 16]");
-  if (batch < 1) return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": batch must be >= 1");
-  if (gs->n_graphs < 1) return fail(ECO_ERR_ARG, "empty graph set");
-  if (gs->edge_weights)
-    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + " with integer weights only (float-weighted sets run up "
-                                                            "to 2048 vertices)");
-  const bool reuse_maxdeg = norm_scope == ECO_NORM_PER_CALL_REUSE;
-  if (reuse_maxdeg) norm_scope = ECO_NORM_PER_CALL;
-  if (norm_scope != ECO_NORM_PER_GRAPH && norm_scope != ECO_NORM_PER_CALL) return fail(ECO_ERR_ARG, "bad norm_scope");
-  if (act && !actions) return fail(ECO_ERR_ARG, "act config without actions buffer");
-  if (!q && !act) return fail(ECO_ERR_ARG, "nothing to compute (q and act both null)");
+    return fail(ECO_ERR_ARG, rows_message(kRowsWg, "forward", "null argument"));
+  if (const int rc = mpnn_rows_check(kRowsWg, "forward", gs, n_obs_in, batch)) return rc;
   if (eco_mpnn_forward_wg_workspace_bytes(gs->n_spins, batch, n_obs_in) == 0)
-    return fail(ECO_ERR_ARG, std::string(kForwardWgRange) + ": batch * rows beyond the 32-bit row index ((2^31 - 1) / 64)");
+    return fail(ECO_ERR_ARG, rows_message(kRowsWg, "forward",
+                                          "batch * rows beyond the 32-bit row index ((2^31 - 1) / 64)"));
   hipStream_t st = (hipStream_t)stream;
-  MpnnArgs a{};
-  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = gs->n_spins; a.gpb = 1;
-  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = norm_scope;
-  a.err = err_word();
-  a.call_maxdeg = (int*)workspace;
-  a.q = q;
-  a.has_act = act != nullptr;
-  if (act) a.act = *act;
-  a.actions = actions;
-  // all-explore workgroups skip their forward only where the actions are the one output (act_skips)
-  a.act_skip = a.has_act && !q && a.act.epsilon > 0.f && !(kernel_paths() & ECO_PATH_NO_ACT_SKIP);
-  if (norm_scope == ECO_NORM_PER_CALL && !reuse_maxdeg)
-    call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)workspace);
+  const FwdHead h = {packed, q, act, actions};
+  MpnnArgs a;
+  int family;
+  bool fused;
+  if (const int rc = forward_setup(&a, &h, 1, n_obs_in, gs, graph_ids, batch, obs_x, norm_scope, nullptr, workspace,
+                                   st, family, fused, true))
+    return rc;
   return launch_large(a, workspace, st);
 }
 
@@ -1837,93 +1845,50 @@ int eco::mpnn_backward_launch(const float* packed, int32_t n_obs_in, const eco_g
   }
 }
 
-// eco_mpnn_grad_large's workspace: a 256 B header (the call's max degree), the SV_* node tensors + MEAN + P, the GR_*
-// tensors + per-graph partials (mpnn_grad_ws_bytes), one [rows_pad][64] gather-source buffer per episode, the
+// The workspace of eco_mpnn_grad_<r.name>: a 256 B header (the call's max degree), the SV_* node tensors + MEAN + P,
+// the GR_* tensors + per-graph partials (mpnn_grad_ws_bytes), one [rows_pad][64] gather-source buffer per episode, the
 // forward's three ping-pong row buffers, the weight-gradient slabs; every part 256 B aligned.  total = 0: no such
-// call (N outside (512, 2048], batch < 1 or batch * n_spins rows beyond the 32-bit row index of the weight gradients).
-static GradLargeLayout grad_rows_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
-  GradLargeLayout L{};
+// call (N outside the range, batch < 1 or batch * n_spins rows beyond the 32-bit row index of the weight gradients:
+// at most (2^31 - 1) / 64 rows, 4095 samples of 8192 vertices).
+GradRowsLayout eco::mpnn_grad_rows_layout(const RowsRange& r, int32_t n_spins, int32_t batch, size_t slab_bytes) {
+  GradRowsLayout L{};
+  if (!rows_in_range(r, n_spins) || batch < 1) return L;
   const size_t RT = (size_t)n_spins * batch;
   if (RT > (size_t)INT32_MAX / 64) return L;
-  const size_t rows_pad = ((size_t)n_spins + 15) & ~(size_t)15;
   L.sv = 256;
   L.gr = L.sv + align_up(sv_mask_offset_floats(RT, batch) * sizeof(float), 256);
   L.g = L.gr + align_up(mpnn_grad_ws_bytes(n_spins, batch), 256);
-  L.hbuf = L.g + (size_t)batch * rows_pad * 64 * sizeof(float);
-  L.slabs = L.hbuf + (size_t)batch * rows_pad * 64 * 3 * sizeof(float);
+  L.hbuf = L.g + rows_buffer_bytes(n_spins, batch, 1);
+  L.slabs = L.hbuf + rows_buffer_bytes(n_spins, batch, 3);
   L.total = L.slabs + slab_bytes;
   return L;
 }
 
-GradLargeLayout eco::mpnn_grad_large_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
-  if (n_spins <= MPNN_MAX_SPINS || n_spins > MPNN_MAX_SPINS_LARGE || batch < 1) return GradLargeLayout{};
-  return grad_rows_layout(n_spins, batch, slab_bytes);
-}
-
-// eco_mpnn_grad_wg's workspace: the same parts in the same order for 2048 < N <= ECO_MAX_SPINS_WG
-GradLargeLayout eco::mpnn_grad_wg_layout(int32_t n_spins, int32_t batch, size_t slab_bytes) {
-  if (!forward_wg_range(n_spins) || batch < 1) return GradLargeLayout{};
-  return grad_rows_layout(n_spins, batch, slab_bytes);
-}
-
-// The launches of eco_mpnn_grad_large before the weight-gradient tail: the call's max degree, the saving forward,
-// the backward over global rows.  8 waves, {float weights} x {8-, 16-float rows} forwards, {float weights} backwards.
-int eco::mpnn_grad_large_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
-                                const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
-                                void* workspace, const GradLargeLayout& L, hipStream_t st) {
+// The launches of eco_mpnn_grad_<r.name> before the weight-gradient tail: the call's max degree, the saving forward,
+// the backward over global rows with a DQ of r.dqcap entries (the float-weight instance exists for the default DQCAP
+// alone: the wg range takes integer weights only).  The kernels walk an episode's rows in loops bounded by N and index
+// across episodes in size_t (DESIGN section 25 has the audit).  The caller has checked the pointers and the range
+// (mpnn_rows_check) and computed the layout.
+int eco::mpnn_grad_rows_launch(const RowsRange& r, const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                               const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
+                               void* workspace, const GradRowsLayout& L, hipStream_t st) {
+  if (!L.total || !rows_in_range(r, gs->n_spins) || (gs->edge_weights && !r.float_weights))
+    return fail(ECO_ERR_ARG, rows_message(r, "grad", "no such call"));
+  static_assert(!kRowsWg.float_weights, "the backward with DQCAP = ECO_MAX_SPINS_WG has no float-weight instance");
   MpnnArgs a;
-  if (const int rc = prepare(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, ECO_NORM_PER_CALL)) return rc;
-  if (!L.total || a.gpb != 1) return fail(ECO_ERR_ARG, "eco_mpnn_grad_large supports 512 < N <= 2048");
+  fill_args(a, packed, n_obs_in, gs, graph_ids, batch, obs_x, ECO_NORM_PER_CALL);
   char* ws = (char*)workspace;
   a.call_maxdeg = (int*)ws;
   a.sv = (float*)(ws + L.sv);
   a.gr = (float*)(ws + L.gr);
   a.dq = dq;
   float* gbuf = (float*)(ws + L.g);
-  float* hbuf = (float*)(ws + L.hbuf);
   call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)ws);
-  const int rows_pad = (a.N + 15) & ~15;
-  const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
-  const bool wide = a.xw == 16, fw = a.gs.edge_weights != nullptr;
-  if (fw) {
-    if (wide) launch_lds(mpnn_forward_large_kernel<8, true, 16, true>, a.B, 512, lds, st, a, hbuf);
-    else launch_lds(mpnn_forward_large_kernel<8, true, 8, true>, a.B, 512, lds, st, a, hbuf);
-    mpnn_backward_large_kernel<8, true><<<a.B, 512, 0, st>>>(a, gbuf);
-  } else {
-    if (wide) launch_lds(mpnn_forward_large_kernel<8, false, 16, true>, a.B, 512, lds, st, a, hbuf);
-    else launch_lds(mpnn_forward_large_kernel<8, false, 8, true>, a.B, 512, lds, st, a, hbuf);
-    mpnn_backward_large_kernel<8, false><<<a.B, 512, 0, st>>>(a, gbuf);
-  }
-  return check_launch("mpnn_grad_large");
-}
-
-// The launches of eco_mpnn_grad_wg before the weight-gradient tail: eco_mpnn_grad_large's sequence on the integer-
-// weight instances, the backward with a DQ of ECO_MAX_SPINS_WG entries.  The kernels walk an episode's rows in loops
-// bounded by N and index across episodes in size_t (DESIGN section 25 has the audit); graphs_per_block is 1 by
-// construction.  The caller has checked the pointers, the range and the layout.
-int eco::mpnn_grad_wg_launch(const float* packed, int32_t n_obs_in, const eco_graph_set* gs, const int32_t* graph_ids,
-                             int32_t batch, const float* obs_x, const float* dq, void* workspace,
-                             const GradLargeLayout& L, hipStream_t st) {
-  if (!L.total || !forward_wg_range(gs->n_spins) || gs->edge_weights)
-    return fail(ECO_ERR_ARG, "eco_mpnn_grad_wg takes 2048 < N <= 8192 with integer weights");
-  MpnnArgs a{};
-  a.P = packed; a.gs = *gs; a.gids = graph_ids; a.B = batch; a.N = gs->n_spins; a.gpb = 1;
-  a.nobs = n_obs_in; a.xw = ECO_OBS_X_STRIDE(n_obs_in); a.x = obs_x; a.norm_scope = ECO_NORM_PER_CALL;
-  a.err = err_word();
-  char* ws = (char*)workspace;
-  a.call_maxdeg = (int*)ws;
-  a.sv = (float*)(ws + L.sv);
-  a.gr = (float*)(ws + L.gr);
-  a.dq = dq;
-  float* gbuf = (float*)(ws + L.g);
-  float* hbuf = (float*)(ws + L.hbuf);
-  call_maxdeg_kernel<<<1, 1024, 0, st>>>(*gs, graph_ids, batch, (int*)ws);
-  const int rows_pad = (a.N + 15) & ~15;
-  const size_t lds = (size_t)readout_scratch_floats(rows_pad, 1, 8, true) * sizeof(float);
-  if (a.xw == 16) launch_lds(mpnn_forward_large_kernel<8, false, 16, true>, a.B, 512, lds, st, a, hbuf);
-  else launch_lds(mpnn_forward_large_kernel<8, false, 8, true>, a.B, 512, lds, st, a, hbuf);
-  mpnn_backward_large_kernel<8, false, ECO_MAX_SPINS_WG><<<a.B, 512, 0, st>>>(a, gbuf);
-  return check_launch("mpnn_grad_wg");
+  launch_forward_large(a, (float*)(ws + L.hbuf), true, st);
+  if (r.dqcap == ECO_MAX_SPINS_WG) mpnn_backward_large_kernel<8, false, ECO_MAX_SPINS_WG><<<a.B, 512, 0, st>>>(a, gbuf);
+  else if (a.gs.edge_weights) mpnn_backward_large_kernel<8, true><<<a.B, 512, 0, st>>>(a, gbuf);
+  else mpnn_backward_large_kernel<8, false><<<a.B, 512, 0, st>>>(a, gbuf);
+  return check_launch("mpnn_grad_rows");
 }
 
 // ---- split2_pk hazard probe (the v_fma_mix inline asm carries its own wait states) ----

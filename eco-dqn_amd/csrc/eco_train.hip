@@ -1004,7 +1004,7 @@ extern "C" size_t eco_mpnn_backward_workspace_bytes(int32_t n_spins, int32_t bat
   return align_up(g, 256) + slab_bytes();
 }
 
-// The weight-gradient tail shared by eco_mpnn_backward and eco_mpnn_grad_large: dW = sum_nodes dY^T X for every Linear
+// The weight-gradient tail shared by eco_mpnn_backward and grad_rows: dW = sum_nodes dY^T X for every Linear
 // from the saved activations `sv` and the activation gradients `gr` (both [tensor][R][64] then per graph, R = batch * N
 // rows), split-K into `slabs` and reduced in a fixed order into grad; then the column sums of the per-graph /
 // per-block partials (nblk rows of DWA).
@@ -1082,64 +1082,45 @@ extern "C" int eco_mpnn_backward(const float* packed, int32_t n_obs_in, const ec
                     slabs, grad, st);
 }
 
+// eco_mpnn_grad_large and eco_mpnn_grad_wg: the gradient on global-memory rows of the range r (RowsRange, eco_mpnn.h).
+// Everything is checked before the first launch; then the call's max degree, the saving forward and the backward
+// (mpnn_grad_rows_launch), then the weight-gradient tail, one DWA row per episode.
+static int grad_rows(const RowsRange& r, const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
+                     const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq, float* grad,
+                     void* workspace, eco_stream_t stream) {
+  if (!packed || !gs || !graph_ids || !obs_x || !dq || !grad || !workspace)
+    return fail(ECO_ERR_ARG, rows_message(r, "grad", "null argument"));
+  if (const int rc = mpnn_rows_check(r, "grad", gs, n_obs_in, batch)) return rc;
+  const int N = gs->n_spins;
+  const GradRowsLayout L = mpnn_grad_rows_layout(r, N, batch, slab_bytes());
+  if (!L.total)
+    return fail(ECO_ERR_ARG, rows_message(r, "grad", "batch * n_spins beyond the 32-bit row index ((2^31 - 1) / 64)"));
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = mpnn_grad_rows_launch(r, packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, workspace, L, st))
+    return rc;
+  char* ws = (char*)workspace;
+  return wgrad_tail((const float*)(ws + L.sv), (const float*)(ws + L.gr), n_obs_in, N, batch, batch, obs_x,
+                    (float*)(ws + L.slabs), grad, st);
+}
+
 extern "C" size_t eco_mpnn_grad_large_workspace_bytes(int32_t n_spins, int32_t batch) {
-  return mpnn_grad_large_layout(n_spins, batch, slab_bytes()).total;
+  return mpnn_grad_rows_layout(kRowsLarge, n_spins, batch, slab_bytes()).total;
 }
 
 extern "C" int eco_mpnn_grad_large(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
                                    const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
                                    float* grad, void* workspace, eco_stream_t stream) {
-  if (!packed || !gs || !graph_ids || !obs_x || !dq || !grad || !workspace)
-    return fail(ECO_ERR_ARG, "eco_mpnn_grad_large: null argument");
-  if (batch < 1) return fail(ECO_ERR_ARG, "batch must be >= 1");
-  const int N = gs->n_spins;
-  if (N <= MPNN_MAX_SPINS || N > MPNN_MAX_SPINS_LARGE)
-    return fail(ECO_ERR_ARG, "eco_mpnn_grad_large supports 512 < N <= 2048 (eco_mpnn_backward below)");
-  const GradLargeLayout L = mpnn_grad_large_layout(N, batch, slab_bytes());
-  if (!L.total) return fail(ECO_ERR_ARG, "batch * n_spins too large");
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = mpnn_grad_large_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, workspace, L, st))
-    return rc;
-  char* ws = (char*)workspace;
-  return wgrad_tail((const float*)(ws + L.sv), (const float*)(ws + L.gr), n_obs_in, N, batch, batch, obs_x,
-                    (float*)(ws + L.slabs), grad, st);
+  return grad_rows(kRowsLarge, packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, grad, workspace, stream);
 }
 
-// The gradient above eco_mpnn_grad_large's range: the same launch sequence and workspace parts on integer-weighted
-// sets of 2048 < N <= ECO_MAX_SPINS_WG vertices (mpnn_grad_wg_launch).  batch * n_spins keeps the 32-bit row index of
-// the weight-gradient jobs: at most (2^31 - 1) / 64 rows, 4095 samples of 8192 vertices.
-static const char* kGradWgRange = "eco_mpnn_grad_wg takes 2048 < N <= 8192";
-
 extern "C" size_t eco_mpnn_grad_wg_workspace_bytes(int32_t n_spins, int32_t batch) {
-  return mpnn_grad_wg_layout(n_spins, batch, slab_bytes()).total;
+  return mpnn_grad_rows_layout(kRowsWg, n_spins, batch, slab_bytes()).total;
 }
 
 extern "C" int eco_mpnn_grad_wg(const float* packed, int32_t n_obs_in, const eco_graph_set* gs,
                                 const int32_t* graph_ids, int32_t batch, const float* obs_x, const float* dq,
                                 float* grad, void* workspace, eco_stream_t stream) {
-  if (!packed || !gs || !graph_ids || !obs_x || !dq || !grad || !workspace)
-    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": null argument");
-  if (!gs->row_ptr || !gs->edge_base || !gs->edges || !gs->deg || !gs->max_deg)
-    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": incomplete graph set");
-  const int N = gs->n_spins;
-  if (N <= ECO_MAX_SPINS || N > ECO_MAX_SPINS_WG)
-    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + " (got N = " + std::to_string(N) +
-                                 "); eco_mpnn_grad_large is the gradient for 512 < N <= 2048");
-  if (n_obs_in < 1 || n_obs_in > ECO_MPNN_MAX_OBS) return fail(ECO_ERR_ARG, "n_obs_in out of range [1, 16]");
-  if (batch < 1) return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": batch must be >= 1");
-  if (gs->n_graphs < 1) return fail(ECO_ERR_ARG, "empty graph set");
-  if (gs->edge_weights)
-    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + " with integer weights only (float-weighted sets train up "
-                                                         "to 2048 vertices)");
-  const GradLargeLayout L = mpnn_grad_wg_layout(N, batch, slab_bytes());
-  if (!L.total)
-    return fail(ECO_ERR_ARG, std::string(kGradWgRange) + ": batch * n_spins beyond the 32-bit row index ((2^31 - 1) / 64)");
-  hipStream_t st = (hipStream_t)stream;
-  if (const int rc = mpnn_grad_wg_launch(packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, workspace, L, st))
-    return rc;
-  char* ws = (char*)workspace;
-  return wgrad_tail((const float*)(ws + L.sv), (const float*)(ws + L.gr), n_obs_in, N, batch, batch, obs_x,
-                    (float*)(ws + L.slabs), grad, st);
+  return grad_rows(kRowsWg, packed, n_obs_in, gs, graph_ids, batch, obs_x, dq, grad, workspace, stream);
 }
 
 extern "C" int eco_dqn_td_weighted(const float* q_s, const float* q_target_next, const int32_t* a_star,

@@ -10,8 +10,8 @@ advances B episodes.  Everything on the step path runs in libecohip:
   train     -> online(s') argmax, target(s') gather, online(s) forward with saved
                activations, TD + MSE / Huber gradient, MPNN backward, optional gradient-norm clipping,
                Adam (dqn.py:403-451); above 512 vertices online(s) is an inference forward and the
-               gradient one self-contained call that recomputes it (MPNN.grad_large; MPNN.grad_wg for 2049 to
-               8192 vertices with train_large_graphs=True)
+               gradient one self-contained call that recomputes it (MPNN.grad_rows; 2049 to 8192 vertices
+               with train_large_graphs=True)
 Schedules are per env-step as in the reference; a vector step advances the
 counter by B.  The replay ratio of the reference (minibatch_size/update_frequency
 samples per env-step, 64/32 = 2 in train_eco.py:136-137) is kept by running
@@ -238,8 +238,8 @@ class DQN:
     # ---------------------------------------------------------------- buffers
     def _alloc_train_buffers(self, m):
         dev = self.device
-        self._wg = self.N > _lib.ECO_MAX_SPINS   # 2049 to ECO_MAX_SPINS_WG vertices: MPNN.grad_wg, no pair forward
-        if self._wg and self.network.grad_wg_bytes(self.N, m) == 0:   # before anything is reallocated
+        self._wg = self.N > _lib.ECO_MAX_SPINS   # 2049 to ECO_MAX_SPINS_WG vertices: no pair forward
+        if self._wg and self.network.grad_rows_bytes(self.N, m) == 0:   # before anything is reallocated
             raise ValueError(f"train_minibatch = {m} samples of N = {self.N} vertices exceed the gradient's row "
                              f"index: train_minibatch * N must be at most (2^31 - 1) / 64 = {(2 ** 31 - 1) // 64} "
                              f"(train_minibatch <= {(2 ** 31 - 1) // 64 // self.N})")
@@ -251,15 +251,12 @@ class DQN:
         self.loss_dev = torch.zeros(1, device=dev)
         if self._prio is not None:
             self.abs_td = torch.empty(m, device=dev)
-        # above 512 vertices the gradient is one self-contained call (MPNN.grad_large) with one workspace; there is
+        # above 512 vertices the gradient is one self-contained call (MPNN.grad_rows) with one workspace; there is
         # no saved-activation buffer between a forward and a backward
         self._large = self.N > _lib.MPNN_MAX_SPINS
-        if self._wg:
+        if self._large:
             self.saved = self.bw_ws = None
-            self.grad_ws = torch.empty(self.network.grad_wg_bytes(self.N, m), dtype=torch.uint8, device=dev)
-        elif self._large:
-            self.saved = self.bw_ws = None
-            self.grad_ws = torch.empty(self.network.grad_large_bytes(self.N, m), dtype=torch.uint8, device=dev)
+            self.grad_ws = torch.empty(self.network.grad_rows_bytes(self.N, m), dtype=torch.uint8, device=dev)
         else:
             self.saved = torch.empty(self.network.saved_bytes(self.N, m), dtype=torch.uint8, device=dev)
             self.bw_ws = torch.empty(_lib.lib.eco_mpnn_backward_workspace_bytes(self.N, m), dtype=torch.uint8,
@@ -365,10 +362,8 @@ class DQN:
                                                     _lib.ptr(loss_dev), _lib.ptr(w), _lib.ptr(self.abs_td),
                                                     _lib.stream_ptr()))
             self._prio.update(self.abs_td)
-        if self._wg:
-            net.grad_wg(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
-        elif self._large:
-            net.grad_large(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
+        if self._large:
+            net.grad_rows(xs, self.graphs, gid, self.dq, self.grad, workspace=self.grad_ws)
         else:
             net.backward_graphs(xs, self.graphs, gid, self.saved, self.dq, self.grad, workspace=self.bw_ws)
         # RCCL sum over xGMI (233.7 KB) on the collective's stream, the mean folded into Adam; independent work

@@ -6,6 +6,7 @@ are views into ONE flat fp32 buffer in state_dict order (58,425 floats for
 n_obs_in=7): the optimiser and the multi-GPU gradient all-reduce work on that
 flat buffer.  torch holds the memory; the forward is libecohip's fused kernel.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -29,6 +30,25 @@ def param_layout(n_obs_in=7):
             ("readout_layer.layers_readout.0.weight", (1, 128)),
             ("readout_layer.layers_readout.0.bias", (1,))]
     return lay
+
+
+class _Timed:
+    """MPNN.timer's record of the launches inside a `with` block (none if the block raises)."""
+
+    def __init__(self, timer, work, graph_ids):
+        self.timer, self.work, self.graph_ids = timer, work, graph_ids
+
+    def __enter__(self):
+        self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        self.ev[0].record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.ev[1].record()
+            self.timer.append((self.ev[0], self.ev[1], self.work, self.graph_ids))
+
+
+_UNTIMED = contextlib.nullcontext()   # no timer list: the launch path pays one attribute test
 
 
 class MPNN(torch.nn.Module):
@@ -117,6 +137,16 @@ class MPNN(torch.nn.Module):
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.flat.device)
         return self._ws
 
+    @staticmethod
+    def _gids(graph_ids):
+        """graph_ids as the contiguous int32 tensor the library reads."""
+        return (graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)).contiguous()
+
+    def _timed(self, work, graph_ids):
+        """Context of one launch: with a timer list set, events around it appended as (start, end, work, graph_ids).
+        work: the batch of a forward, twice the batch of a pair, minus the batch of a backward or gradient call."""
+        return _UNTIMED if self.timer is None else _Timed(self.timer, work, graph_ids)
+
     # ---- fast path: graphs resident in a GraphStore ----
     def forward_graphs(self, obs_x, graphs, graph_ids, norm_scope=_lib.ECO_NORM_PER_GRAPH, q_out=None,
                        act=None, actions_out=None, saved=None, stream=None):
@@ -128,26 +158,21 @@ class MPNN(torch.nn.Module):
         self._ensure_packed(stream)
         if q_out is None and act is None:
             q_out = torch.empty(B, N, dtype=torch.float32, device=obs_x.device)
-        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
-        if self.timer is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        if N > _lib.ECO_MAX_SPINS:   # inference above 2048 vertices: eco_mpnn_forward_wg, picked by N alone
-            if saved is not None:
-                raise ValueError(f"training forward (saved activations) supports N <= {_lib.MPNN_MAX_SPINS}; inference "
-                                 f"runs {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG}, got N = {N}")
-            _lib.check(_lib.lib.eco_mpnn_forward_wg(
-                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-                _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
-                _lib.ptr(actions_out), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
-        else:
-            _lib.check(_lib.lib.eco_mpnn_forward(
-                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-                _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
-                _lib.ptr(actions_out), _lib.ptr(saved), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
-        if self.timer is not None:
-            ev[1].record()
-            self.timer.append((ev[0], ev[1], B, graph_ids))
+        gids = self._gids(graph_ids)
+        with self._timed(B, graph_ids):
+            if N > _lib.ECO_MAX_SPINS:   # inference above 2048 vertices: eco_mpnn_forward_wg, picked by N alone
+                if saved is not None:
+                    raise ValueError(f"training forward (saved activations) supports N <= {_lib.MPNN_MAX_SPINS}; "
+                                     f"inference runs {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG}, got N = {N}")
+                _lib.check(_lib.lib.eco_mpnn_forward_wg(
+                    _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids), B,
+                    _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
+                    _lib.ptr(actions_out), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
+            else:
+                _lib.check(_lib.lib.eco_mpnn_forward(
+                    _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids), B,
+                    _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out), ctypes.byref(act) if act is not None else None,
+                    _lib.ptr(actions_out), _lib.ptr(saved), _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
         return q_out
 
     def forward_pair_graphs(self, other, obs_x, graphs, graph_ids, norm_scope=_lib.ECO_NORM_PER_GRAPH, q_out=None,
@@ -166,19 +191,14 @@ class MPNN(torch.nn.Module):
             q_out = torch.empty(B, N, dtype=torch.float32, device=obs_x.device)
         if q_out_other is None and act_other is None:
             q_out_other = torch.empty(B, N, dtype=torch.float32, device=obs_x.device)
-        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
-        if self.timer is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(_lib.lib.eco_mpnn_forward_pair(
-            _lib.ptr(self.packed), _lib.ptr(other.packed), self.n_obs_in, ctypes.byref(graphs.gs),
-            _lib.ptr(gids.contiguous()), B, _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out),
-            ctypes.byref(act) if act is not None else None, _lib.ptr(actions_out), _lib.ptr(q_out_other),
-            ctypes.byref(act_other) if act_other is not None else None, _lib.ptr(actions_out_other),
-            _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
-        if self.timer is not None:
-            ev[1].record()
-            self.timer.append((ev[0], ev[1], 2 * B, graph_ids))  # two forwards' work
+        gids = self._gids(graph_ids)
+        with self._timed(2 * B, graph_ids):   # two forwards' work
+            _lib.check(_lib.lib.eco_mpnn_forward_pair(
+                _lib.ptr(self.packed), _lib.ptr(other.packed), self.n_obs_in, ctypes.byref(graphs.gs),
+                _lib.ptr(gids), B, _lib.ptr(obs_x), norm_scope, _lib.ptr(q_out),
+                ctypes.byref(act) if act is not None else None, _lib.ptr(actions_out), _lib.ptr(q_out_other),
+                ctypes.byref(act_other) if act_other is not None else None, _lib.ptr(actions_out_other),
+                _lib.ptr(self._workspace(N, B)), _lib.stream_ptr(stream)))
         return q_out, q_out_other
 
     @staticmethod
@@ -193,18 +213,50 @@ class MPNN(torch.nn.Module):
         need = _lib.lib.eco_mpnn_backward_workspace_bytes(N, B)
         if workspace is None or workspace.numel() < need:
             workspace = torch.empty(need, dtype=torch.uint8, device=obs_x.device)
-        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
-        if self.timer is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(_lib.lib.eco_mpnn_backward(
-            _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-            _lib.ptr(obs_x), _lib.ptr(saved), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace),
-            _lib.stream_ptr(stream)))
-        if self.timer is not None:
-            ev[1].record()
-            self.timer.append((ev[0], ev[1], -B, graph_ids))   # negative batch marks a backward launch
+        gids = self._gids(graph_ids)
+        with self._timed(-B, graph_ids):   # negative batch marks a backward launch
+            _lib.check(_lib.lib.eco_mpnn_backward(
+                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids), B,
+                _lib.ptr(obs_x), _lib.ptr(saved), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace),
+                _lib.stream_ptr(stream)))
         return grad_out
+
+    # ---- the gradient on global-memory rows: eco_mpnn_grad_large (512 < N <= 2048), eco_mpnn_grad_wg (to 8192) ----
+    # entry suffix -> (N above, N up to, where the sizes below go)
+    _GRAD_ROWS = {"large": (_lib.MPNN_MAX_SPINS, _lib.ECO_MAX_SPINS, "backward_graphs is the gradient for N <= 512"),
+                  "wg": (_lib.ECO_MAX_SPINS, _lib.ECO_MAX_SPINS_WG,
+                         f"grad_large is the gradient for 512 < N <= {_lib.ECO_MAX_SPINS}")}
+
+    def _grad_rows(self, entry, obs_x, graphs, graph_ids, dq, grad_out, workspace, stream):
+        B, N = obs_x.shape[0], obs_x.shape[1]
+        self._check_x(obs_x)
+        self._ensure_packed(stream)
+        need = getattr(_lib.lib, f"eco_mpnn_grad_{entry}_workspace_bytes")(N, B)
+        if need == 0:
+            lo, hi, below = self._GRAD_ROWS[entry]
+            raise ValueError(f"grad_{entry} takes {lo} < N <= {hi} and batch * N <= (2^31 - 1) / 64 "
+                             f"(got N = {N}, batch = {B}); {below}")
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=obs_x.device)
+        gids = self._gids(graph_ids)
+        with self._timed(-B, graph_ids):   # negative batch marks a backward launch
+            _lib.check(getattr(_lib.lib, f"eco_mpnn_grad_{entry}")(
+                _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids), B,
+                _lib.ptr(obs_x), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace), _lib.stream_ptr(stream)))
+        return grad_out
+
+    @staticmethod
+    def grad_rows_bytes(n_spins, batch):
+        """Workspace bytes of grad_rows (0: not a size it takes)."""
+        return (MPNN.grad_wg_bytes if n_spins > _lib.ECO_MAX_SPINS else MPNN.grad_large_bytes)(n_spins, batch)
+
+    def grad_rows(self, obs_x, graphs, graph_ids, dq, grad_out, workspace=None, stream=None):
+        """loss.backward() for 512 < N <= 8192: grad_out[flat] = d(sum dq . Q)/dparams, Q the network's output on
+        obs_x under norm_scope=ECO_NORM_PER_CALL.  One self-contained call: it recomputes the forward inside itself,
+        so there is no `saved` buffer; Q for the TD error comes from forward_graphs.  grad_large up to 2048 vertices,
+        grad_wg above (integer-weighted graphs; about 27 x rows_pad x 256 B of workspace per sample, 56.6 MB at 8192)."""
+        entry = "wg" if obs_x.shape[1] > _lib.ECO_MAX_SPINS else "large"
+        return self._grad_rows(entry, obs_x, graphs, graph_ids, dq, grad_out, workspace, stream)
 
     @staticmethod
     def grad_large_bytes(n_spins, batch):
@@ -212,29 +264,8 @@ class MPNN(torch.nn.Module):
         return _lib.lib.eco_mpnn_grad_large_workspace_bytes(n_spins, batch)
 
     def grad_large(self, obs_x, graphs, graph_ids, dq, grad_out, workspace=None, stream=None):
-        """loss.backward() for 512 < N <= 2048: grad_out[flat] = d(sum dq . Q)/dparams, Q the network's output on
-        obs_x under norm_scope=ECO_NORM_PER_CALL.  One self-contained call (eco_mpnn_grad_large): it recomputes the
-        forward inside itself, so there is no `saved` buffer; Q for the TD error comes from forward_graphs."""
-        B, N = obs_x.shape[0], obs_x.shape[1]
-        self._check_x(obs_x)
-        self._ensure_packed(stream)
-        need = self.grad_large_bytes(N, B)
-        if need == 0:
-            raise ValueError(f"grad_large takes 512 < N <= {_lib.ECO_MAX_SPINS} and batch * N <= (2^31 - 1) / 64 "
-                             f"(got N = {N}, batch = {B}); backward_graphs is the gradient for N <= 512")
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(need, dtype=torch.uint8, device=obs_x.device)
-        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
-        if self.timer is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(_lib.lib.eco_mpnn_grad_large(
-            _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-            _lib.ptr(obs_x), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace), _lib.stream_ptr(stream)))
-        if self.timer is not None:
-            ev[1].record()
-            self.timer.append((ev[0], ev[1], -B, graph_ids))   # negative batch marks a backward launch
-        return grad_out
+        """grad_rows for 512 < N <= 2048 alone (eco_mpnn_grad_large)."""
+        return self._grad_rows("large", obs_x, graphs, graph_ids, dq, grad_out, workspace, stream)
 
     @staticmethod
     def grad_wg_bytes(n_spins, batch):
@@ -242,30 +273,8 @@ class MPNN(torch.nn.Module):
         return _lib.lib.eco_mpnn_grad_wg_workspace_bytes(n_spins, batch)
 
     def grad_wg(self, obs_x, graphs, graph_ids, dq, grad_out, workspace=None, stream=None):
-        """grad_large for 2048 < N <= 8192 (eco_mpnn_grad_wg): the same self-contained gradient under
-        norm_scope=ECO_NORM_PER_CALL, on integer-weighted graphs.  The workspace is about 27 x rows_pad x 256 B per
-        sample (56.6 MB at 8192 vertices)."""
-        B, N = obs_x.shape[0], obs_x.shape[1]
-        self._check_x(obs_x)
-        self._ensure_packed(stream)
-        need = self.grad_wg_bytes(N, B)
-        if need == 0:
-            raise ValueError(f"grad_wg takes {_lib.ECO_MAX_SPINS} < N <= {_lib.ECO_MAX_SPINS_WG} and batch * N <= "
-                             f"(2^31 - 1) / 64 (got N = {N}, batch = {B}); grad_large is the gradient for 512 < N <= "
-                             f"{_lib.ECO_MAX_SPINS}")
-        if workspace is None or workspace.numel() < need:
-            workspace = torch.empty(need, dtype=torch.uint8, device=obs_x.device)
-        gids = graph_ids if graph_ids.dtype == torch.int32 else graph_ids.to(torch.int32)
-        if self.timer is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        _lib.check(_lib.lib.eco_mpnn_grad_wg(
-            _lib.ptr(self.packed), self.n_obs_in, ctypes.byref(graphs.gs), _lib.ptr(gids.contiguous()), B,
-            _lib.ptr(obs_x), _lib.ptr(dq), _lib.ptr(grad_out), _lib.ptr(workspace), _lib.stream_ptr(stream)))
-        if self.timer is not None:
-            ev[1].record()
-            self.timer.append((ev[0], ev[1], -B, graph_ids))   # negative batch marks a backward launch
-        return grad_out
+        """grad_rows for 2048 < N <= 8192 alone (eco_mpnn_grad_wg)."""
+        return self._grad_rows("wg", obs_x, graphs, graph_ids, dq, grad_out, workspace, stream)
 
     # ---- reference-format forward (drop-in for mpnn.py:40-77) ----
     def forward(self, obs):
