@@ -17,7 +17,9 @@
 // Weights: +-1 fair per edge (EdgeType.DISCRETE, symmetric hash), 1 (UNIFORM), or float64 uniform in (-1, 1)
 // (EdgeType.RANDOM): w = 2u - 1, u the top 53 bits of the same symmetric hash, written to gs.edge_weights with
 // sign(w) in the packed word.
-// Parity is distributional only (different RNG streams from numpy/networkx).
+// Parity with numpy/networkx is distributional only (different RNG streams).  What these kernels themselves draw is
+// an exact function of (seed, slot, pair or draw number): oracle/graphgen_oracle.py restates it, and
+// tests/test_graphgen_exact_gpu.py holds every edge word, weight and prepared field to it bit for bit.
 #include "eco_common.h"
 
 namespace eco {
@@ -105,15 +107,18 @@ __global__ void er_scan_kernel(int first, int count, int N, const int32_t* row_c
 
 // pass 3: fill sorted columns (wave per row)
 __global__ void er_fill_kernel(int first, int count, int N, float p, uint64_t seed, int kind,
-                               const int32_t* row_ptr, const int64_t* edge_base, uint32_t* edges, double* weights,
-                               long long cap) {
+                               const int32_t* row_ptr, const int64_t* edge_base, uint32_t* edges, double* weights) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= (long long)count * N) return;
   const int g = first + (int)(row / N);
   const int i = (int)(row % N);
   const int32_t* rp = row_ptr + (size_t)g * (N + 1);
-  if (rp[N] > cap) return;
+  // er_scan_kernel ran before on the same stream and wrote rp[N] for every graph of the call: 0 for a graph without
+  // an edge and for one that overflowed its slot (whose whole row_ptr row it zeroed).  Either way there is nothing to
+  // fill; going on would put every row of an overflowing graph at offset 0 of the slot, deg_i entries each, past the
+  // slot's end when deg_i > cap.
+  if (rp[N] == 0) return;
   uint32_t* ed = edges + edge_base[g];
   double* ew = weights ? weights + edge_base[g] : nullptr;
   int pos = rp[i];
@@ -410,7 +415,7 @@ extern "C" int eco_graphs_generate(eco_graph_set* gs, int32_t first, int32_t cou
     er_count_kernel<<<rblocks, 256, 0, st>>>(first, count, N, (float)param, seed, cnt);
     er_scan_kernel<<<(count + 3) / 4, 256, 0, st>>>(first, count, N, cnt, rp, edge_cap, err);
     er_fill_kernel<<<rblocks, 256, 0, st>>>(first, count, N, (float)param, seed, weight_kind, rp, gs->edge_base,
-                                            ed, ewt, edge_cap);
+                                            ed, ewt);
   } else if (kind == ECO_GRAPH_BA) {
     const int m = (int)param;
     if (m < 1 || m >= N || m > 64) return fail(ECO_ERR_ARG, "BA m must be in [1, min(N-1, 64)]");
