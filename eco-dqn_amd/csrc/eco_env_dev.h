@@ -65,7 +65,7 @@ __device__ __forceinline__ double obs_value(int id, const ObsCtx& c, int s, F h,
 }
 
 // ---- generic scorers (eco_env_problems.hip; the table of F_i, quality and invalidity masks is at its top) ----
-// shared with the compact replay ring of eco_train.hip, which rebuilds observation rows with these statements
+// shared with the compact replay ring of eco_replay.hip, which rebuilds observation rows with these statements
 __device__ __forceinline__ bool target_maximises(int t) {
   return t == ECO_TARGET_MAX_IND_SET || t == ECO_TARGET_MAX_CLIQUE;
 }

@@ -5,7 +5,8 @@
 // strictly sequential structure (every add / priority update is an up-/down-heap walk whose path depends on
 // the previous one), so it lives here as a native host structure of two flat arrays (buffer position and
 // td error per heap position); the transitions stay resident in HBM in the fp32 feature ring (eco_replay,
-// slot = buffer position - 1) and a sample is one gather kernel over the chosen slots.  Every heap
+// slot = buffer position - 1) and a sample is one gather kernel over the chosen slots (eco_replay_gather,
+// eco_replay.hip).  Every heap
 // operation follows the reference's comparisons exactly (strict `<` / `>`, the `< size` bound of
 // down_heap, the max-td lookup of a heap position that never exists) so the heap layout, partitions,
 // probabilities and importance weights match the reference call for call (tests/test_per_cpu.py against
@@ -278,43 +279,4 @@ extern "C" int32_t eco_per_partitions(const eco_per* p, int32_t* bounds, double*
   if (probs)
     for (size_t i = 0; i < p->probs.size(); ++i) probs[i] = p->probs[i];
   return p->n_parts;
-}
-
-// ---------------------------------------------------------------------------------------- device gather ----
-// The sampled transitions out of the fp32 feature ring (eco_replay) by explicit slot: one workgroup per
-// sample, float4 copies of the s / s' node-feature rows (HBM-bound: 2 x N x x_stride x 4 B per sample).
-__global__ __launch_bounds__(256) void replay_gather_kernel(eco_replay rb, int M, const int32_t* slots, float* xs,
-                                                           float* xn, int32_t* gid, int32_t* act, float* rew,
-                                                           float* done) {
-  const int m = blockIdx.x;
-  if (m >= M) return;
-  const int xst = rb.x_stride == 16 ? 16 : 8;
-  const int slot = slots[m];
-  if (slot < 0 || slot >= rb.capacity) return;  // rejected on the host; never read outside the ring
-  const int per = rb.n_spins * xst / 4;
-  const float4* s4 = reinterpret_cast<const float4*>(rb.xs + (size_t)slot * rb.n_spins * xst);
-  const float4* n4 = reinterpret_cast<const float4*>(rb.xn + (size_t)slot * rb.n_spins * xst);
-  float4* ds = reinterpret_cast<float4*>(xs + (size_t)m * rb.n_spins * xst);
-  float4* dn = reinterpret_cast<float4*>(xn + (size_t)m * rb.n_spins * xst);
-  for (int i = threadIdx.x; i < per; i += blockDim.x) {
-    ds[i] = s4[i];
-    dn[i] = n4[i];
-  }
-  if (threadIdx.x == 0) {
-    gid[m] = rb.gid[slot];
-    act[m] = rb.act[slot];
-    rew[m] = rb.rew[slot];
-    done[m] = rb.done[slot];
-  }
-}
-
-// slots: DEVICE int32 [m], each in [0, capacity) (host-checked by the Python wrapper from the buffer
-// positions eco_per_sample returned).
-extern "C" int eco_replay_gather(const eco_replay* rb, int32_t m, const int32_t* slots, float* xs, float* xn,
-                                 int32_t* graph_ids, int32_t* actions, float* rewards, float* dones,
-                                 eco_stream_t stream) {
-  if (m < 0 || rb->capacity < 1) return fail(ECO_ERR_ARG, "replay gather: bad size");
-  if (m == 0) return ECO_OK;
-  replay_gather_kernel<<<m, 256, 0, (hipStream_t)stream>>>(*rb, m, slots, xs, xn, graph_ids, actions, rewards, dones);
-  return check_launch("replay_gather");
 }

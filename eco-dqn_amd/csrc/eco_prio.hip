@@ -1,6 +1,6 @@
 // Proportional prioritised replay on the device (Schaul et al. 2016, the variant that needs sums and no sort).
 // One uint32 `mass` per LOGICAL ring position x (transition k of the buffer's life sits at x = k % capacity: the
-// index replay_sample_kernel / replay_compact_sample_kernel call x), so one index space serves the fp32 feature
+// index replay_sample_kernel / replay_compact_read_kernel of eco_replay.hip call x), so one index space serves the fp32 feature
 // ring and the compact ring.  mass = clamp(rint((min(|d|, d_max) + eps)^alpha * 2^16), 1, 2^31 - 1) for a stored
 // transition, 0 for a never-written slot; every sum is a uint64 (capacity * 2^31 < 2^63), so the sampler does not
 // depend on the reduction order and is restated exactly on the CPU (tests/prio_common.py).  No atomics at all.

@@ -1,5 +1,5 @@
 """Compact replay ring for the five set-problem targets (MIN_COVER, MIN_CUT, MAX_IND_SET, MAX_CLIQUE, MIN_DOM_SET;
-csrc/eco_train.hip "compact replay, generic scorers").
+csrc/eco_replay.hip, ProbRing).
 
 The oracle is the fp32 feature ring fed by the same pushes: its rows are the env's own, and the env is pinned to the
 reference in tests/test_problems_gpu.py.  Every comparison is bitwise (float32 viewed as int32), so there is no

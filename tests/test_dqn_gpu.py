@@ -409,7 +409,7 @@ def test_compact_replay_matches_feature_replay(n, B, basis, kind):
     features bitwise, actions, rewards, dones, graph ids -- across a masked reset (new s rows) and a
     ring wrap.  The compact ring stores one state per transition: 4N + 80 B against 64N B (<= 1 KB at N=200).
     N = 257 and BA-500 (configs[3]) take the sample kernel's 128-thread path for N > 256 (several vertices per
-    thread, csrc/eco_train.hip replay_compact_sample)."""
+    thread, csrc/eco_replay.hip replay_compact_read_kernel)."""
     from eco_hip.graphs import GraphStore
     from eco_hip.envs.batched import VecSpinSystem
     from eco_hip.envs.utils import (DEFAULT_OBSERVABLES, RewardSignal, ExtraAction, OptimisationTarget,

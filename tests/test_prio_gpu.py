@@ -392,6 +392,65 @@ def test_both_rings_give_one_minibatch_for_one_idx():
     assert b[2].tolist()[1:3] == [-9, -9] and float(b[0][1].max()) == -9 and b[2].tolist()[0] >= 0
 
 
+def test_cut_gather_on_the_128_thread_path():
+    """eco_replay_compact_gather on a MaxCut ring above 256 vertices (128 threads, several vertices per thread;
+    the test above stays on the 64-thread path): for positions drawn with duplicates, across a masked reset and a
+    ring wrap, the rows equal the feature ring's eco_replay_gather bit for bit, and the rows of the two positions
+    outside [0, len(ring)) keep what they held."""
+    from eco_hip import _lib
+    from eco_hip.graphs import GraphStore
+    from eco_hip.envs.batched import VecSpinSystem
+    from eco_hip.envs.utils import (DEFAULT_OBSERVABLES, RewardSignal, ExtraAction, OptimisationTarget,
+                                    SpinBasis)
+    from eco_hip.agents.dqn.utils import ReplayBuffer, CompactReplayBuffer
+    n, B, m = 257, 12, 40
+    C = 5 * B
+    store = GraphStore.random("ER", 2 * B, n, 0.15, seed=n)
+    env = VecSpinSystem(store, B, 2 * n, observables=DEFAULT_OBSERVABLES, reward_signal=RewardSignal.BLS,
+                        extra_action=ExtraAction.NONE, optimisation_target=OptimisationTarget.CUT,
+                        spin_basis=SpinBasis.SIGNED, norm_rewards=True, basin_reward=1. / n)
+    feat = ReplayBuffer(C, n, device="cuda", seed=17)
+    comp = CompactReplayBuffer(C, env, seed=17)
+    env.reset(graph_ids=np.arange(B), seed=3)
+    comp.snapshot()
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = env.obs_x.clone()
+    for t in range(8):             # 96 transitions into a ring of 60: wraps
+        acts = torch.randint(0, n, (B,), generator=g, device="cuda", dtype=torch.int32)
+        nxt = torch.empty_like(x)
+        _, rew, done = env.step(acts, obs_out=nxt)
+        feat.add_batch(x, nxt, env.graph_ids, acts, rew, done)
+        comp.add_step(acts, rew, done)
+        x = nxt.clone()
+        if t == 3:                 # masked reset of half the episodes onto new graphs
+            mask = (torch.arange(B, device="cuda") % 2).to(torch.uint8)
+            env.reset(graph_ids=np.arange(B) + B, mask=mask, seed=9)
+            comp.snapshot(mask)
+            x = env.obs_x.clone()
+    env.check_errors()
+    assert len(feat) == len(comp) == C
+    pos = np.random.default_rng(11).integers(0, C, m).astype(np.int32)   # duplicates included
+    assert len(set(pos.tolist())) < m
+    pos[7], pos[23] = -1, C
+    keep = np.flatnonzero((pos >= 0) & (pos < C))
+    assert len(keep) == m - 2
+    idx, idx_in = torch.from_numpy(pos).cuda(), torch.from_numpy(pos[keep]).cuda()
+    a, b = feat._buffers(len(keep)), comp._buffers(m)
+    for t in a + b:
+        t.fill_(-9)
+    _lib.check(_lib.lib.eco_replay_gather(ctypes.byref(feat.rb), len(keep), _lib.ptr(idx_in),
+                                          *(_lib.ptr(t) for t in a), _lib.stream_ptr()))
+    _lib.check(_lib.lib.eco_replay_compact_gather(
+        ctypes.byref(env.cfg), _lib.ptr(env.state), ctypes.byref(store.gs), B, _lib.ptr(comp.ring), C, len(comp),
+        comp._pushed, m, _lib.ptr(idx), *(_lib.ptr(t) for t in b), _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    kd = torch.from_numpy(keep).cuda()
+    assert _same(a, [t[kd] for t in b])    # features of s and s', graph id, action, reward, done
+    assert float(a[0].abs().max()) > 0 and int(a[2].min()) >= 0
+    for t in b:
+        assert bool((t[[7, 23]] == -9).all())
+
+
 # ------------------------------------------------------------------ end to end
 @pytest.mark.parametrize("alpha", [0.6, 0.0])
 @pytest.mark.parametrize("compact", [True, False])
