@@ -201,64 +201,6 @@ __global__ void build_time_table_kernel(uint8_t* state, size_t off_tab, int T) {
   *hdr = T;
 }
 
-template <int VPT, class F>
-__device__ __forceinline__ void write_obs(const EnvArgs& a, int e, int lane, const int (&s)[VPT], const F (&h)[VPT],
-                                          const int (&tsf)[VPT], const ObsCtx& c) {
-  const int N = a.cfg.n_spins;
-  const int nobs = a.cfg.n_obs;
-  const double* tab = tab_ptr(a);
-#pragma unroll
-  for (int k = 0; k < VPT; ++k) {
-    const int v = lane + 64 * k;
-    if (v >= N) continue;
-    float xf[ECO_MAX_OBS];
-#pragma unroll
-    for (int i = 0; i < ECO_MAX_OBS; ++i) {
-      double val = 0.0;
-      if (i < nobs) {
-        val = obs_value(a.cfg.obs_ids[i], c, s[k], h[k], tsf[k], tab);
-        if (a.obs_f64) a.obs_f64[((size_t)e * nobs + i) * N + v] = val;
-      }
-      xf[i] = (float)val;
-    }
-    if (a.obs_x) store_obs_row(a.obs_x, (size_t)e * N + v, nobs, xf);
-  }
-}
-
-// write_obs for DEFAULT_OBSERVABLES (spinsystem.py:486-535 with the ECO training observables, the hot path) and no
-// float64 rows: the fp32 feature rows directly.  Per vertex only three values vary -- the spin (basis-mapped), the
-// immediate quality change g / mlr and the time since flip -- and the other four are wave-uniform, converted
-// once.  g / mlr is the correctly rounded f32 quotient of the two integers (exact in f32: |g|, |mlr| < 2^18),
-// which equals the reference's float64 quotient rounded to f32: the exact quotient of integers below 2^18 is
-// never within 2^-53 of an f32 rounding midpoint without being one (its distance from any K / 2^j is at least
-// 2^-42 relative), so rounding through float64 cannot change the f32 result.  -0.0 is kept (the product is a
-// float product: s = -1, h = 0 gives -0.0, as the reference's float64 product does).  tests/test_env_gpu.py
-// checks these rows bitwise against the general path.  None of that carries over to float weights (F = double):
-// there s * h / mlr is computed in float64, as the general path does, and rounded once to f32.
-template <int VPT, class F>
-__device__ __forceinline__ void write_obs_default(const EnvArgs& a, int e, int lane, const int (&s)[VPT],
-                                                  const F (&h)[VPT], const int (&tsf)[VPT], const ObsCtx& c) {
-  const int N = a.cfg.n_spins;
-  const double* tab = tab_ptr(a);
-  const float mlrf = (float)c.mlr;
-  const float u3 = (float)c.dist_best, u4 = (float)c.hamming, u5 = (float)c.nqi, u6 = (float)c.term;
-  const bool binary = c.basis == ECO_BASIS_BINARY;
-#pragma unroll
-  for (int k = 0; k < VPT; ++k) {
-    const int v = lane + 64 * k;
-    if (v >= N) continue;
-    const float sf = (float)s[k];
-    const float x0 = binary ? (float)((1 - s[k]) / 2) : sf;  // (1 - s) / 2 is exact: 0 or 1
-    float x1;
-    if constexpr (std::is_same_v<F, int>) x1 = __fdiv_rn(sf * (float)h[k], mlrf);
-    else x1 = (float)(((double)s[k] * h[k]) / c.mlr);
-    const float x2 = (float)tab[tsf[k]];
-    float4* dst = (float4*)(a.obs_x + ((size_t)e * N + v) * 8);
-    dst[0] = make_float4(x0, x1, x2, u3);
-    dst[1] = make_float4(u4, u5, u6, 0.f);
-  }
-}
-
 // SpinSystemBase.reset (spinsystem.py:183-259) + _reset_state (:283-330)
 // F = int: integer weights (the packed byte); F = double: float-weighted sets (gs.edge_weights), every quantity the
 // reference computes in float64 computed in float64 here.
@@ -289,23 +231,13 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
     const int v = lane + 64 * k;
     int sv = 0;
     if (v < N) {
-      if (a.spins_in) {
-        sv = a.spins_in[(size_t)e * N + v];
-        if (sv != 1 && sv != -1) { atomicCAS(a.err, 0, ECO_ERR_BASIS); sv = -1; }
-      } else if (a.cfg.reversible_spins) {
-        sv = (int)(rng3(a.seed, (uint64_t)e, (uint64_t)v) >> 63) * 2 - 1;  // 2*randint(2)-1
-      } else {
-        sv = -1;  // irreversible: all -1 (spinsystem.py:295-297)
-      }
+      sv = initial_spin(a, e, v);
       my_s[v] = (int8_t)sv;
     }
     s[k] = sv;
     tsf[k] = 0;
   }
-  // each wave reads back only its own LDS slice: a wave-scope fence suffices
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  wave_lds_sync();
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
   std::conditional_t<FW, double, long long> sg = 0;
@@ -338,34 +270,22 @@ __global__ __launch_bounds__(256) void env_reset_kernel(EnvArgs a) {
   const double lbabs = lb < 0.0 ? -lb : lb;
   const double score = cut + lbabs;        // MaximizationProblem.get_score (score_solver.py:182-188)
   const double nscore = score / qn;        // get_normalized_score (:190-194)
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  F* gh = (F*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<F> rows(a, e);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    if (v < N) { gsp[v] = (int8_t)s[k]; gh[v] = h[k]; gt[v] = 0; gb[v] = (int8_t)s[k]; }
+    if (v < N) { rows.spins[v] = (int8_t)s[k]; rows.field[v] = h[k]; rows.tsf[v] = 0; rows.best[v] = (int8_t)s[k]; }
   }
   uint32_t* vidx = (uint32_t*)(a.state + L.off_vidx) + (size_t)e * L.cap;
   for (int i = lane; i < L.cap; i += 64) vidx[i] = 0u;
-  if (lane == 0) {
-    EpScal* sc = scal_ptr(a) + e;
-    sc->score = score; sc->nscore = nscore;
-    sc->best_score = score; sc->best_nscore = nscore; sc->best_solution = cut;
-    sc->mlr = mlr; sc->qn = qn; sc->lbabs = lbabs;
-    sc->hash = 0ull; sc->t = 0; sc->hamming = 0; sc->graph = gid; sc->done = 0; sc->early = 0;
-    sc->visit_count = 0;
-    sc->inorm = 1.0; sc->lb = lb; sc->inv = 0; sc->best_inv = 0;
-  }
   int n1 = 0;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) n1 += __popcll(__ballot(s[k] > 0));
-  if (lane == 0) { (scal_ptr(a) + e)->n1 = n1; (scal_ptr(a) + e)->best_n1 = n1; }
+  if (lane == 0) store_reset_scalars(scal_ptr(a) + e, score, nscore, cut, mlr, qn, lb, 1.0, gid, n1, 0);
   ObsCtx c;
   c.mlr = mlr; c.dist_best = 0.0; c.hamming = 0.0; c.nqi = (double)cnt / (double)N;
   c.term = 0.0; c.ep_time = 0.0; c.basis = a.cfg.spin_basis;
-  write_obs<VPT, F>(a, e, lane, s, h, tsf, c);
+  write_obs<VPT, 64, F>(a, e, lane, s, h, tsf, c);
 }
 
 // Optional per-phase stamps of env_step_kernel (timing build only: make timing; tools/r04/env_timing.py):
@@ -398,8 +318,6 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
   if (e >= a.B) return;
   ECO_ENV_TS(0);
   const int N = a.cfg.n_spins;
-  const int T = a.cfg.max_steps;
-  const EnvLayout& L = a.L;
   EpScal* sc = scal_ptr(a) + e;
   const int act = uniform_i(a.actions[e]);  // loaded alongside the done flag
   if (sc->done) {  // auto-masked
@@ -411,10 +329,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
     return;
   }
   const int t = sc->t + 1;  // :362
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  F* gh = (F*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<F> rows(a, e);
   const int gid = sc->graph;
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
@@ -424,7 +339,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    if (v < N) { s[k] = gsp[v]; h[k] = gh[v]; tsf[k] = gt[v]; bs[k] = gb[v]; }
+    if (v < N) { s[k] = rows.spins[v]; h[k] = rows.field[v]; tsf[k] = rows.tsf[v]; bs[k] = rows.best[v]; }
     else { s[k] = 0; h[k] = 0; tsf[k] = 0; bs[k] = 0; }
   }
   int sa_old;
@@ -468,73 +383,52 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& a) {
 #pragma unroll
     for (int k = 0; k < VPT; ++k) c += __popcll(__ballot(s[k] < 0)); return c; }();
   // HistoryBuffer.update (utils.py:444-464): is the flipped set (== spin configuration) new?
-  // (the f64 step probes the visited set here, without the early first-slot load: the probe record that
-  // history_update_from carries across the field update is the integer kernels' one stack object)
+  // (the f64 step probes the visited set here, without the early first-slot load of the integer kernels)
   bool isnew = true;
   if constexpr (FW) { if (track) isnew = history_update<VPT>(a, e, lane, sc, act, words); }
   else isnew = track ? history_update_from<VPT>(a, e, lane, sc, hp, words) : true;
   ECO_ENV_TS(3);
-  // reward (:418-457)
-  double best_score = sc->best_score, best_nscore = sc->best_nscore;
-  double rew = 0.0;
-  int early = sc->early + 1;
-  const bool improved = score > best_score;
-  if (improved) {
-    early = 0;
-    if (a.cfg.reward_signal == ECO_REWARD_BLS)
-      rew = a.cfg.norm_rewards ? nscore - best_nscore : score - best_score;
-  }
-  if (a.cfg.reward_signal == ECO_REWARD_DENSE) rew = a.cfg.norm_rewards ? delta_n : delta;
-  if (a.cfg.has_stag_punishment && !isnew) rew -= a.cfg.stag_punishment;
-  if (a.cfg.has_basin_reward && cnt == 0 && isnew) rew += a.cfg.basin_reward;
-  // best tracking (:459-477)
+  // reward, best tracking, termination (:418-477, :541-556)
+  const StepOutcome o = step_outcome(a.cfg, t, score, nscore, delta, delta_n, sc->best_score, sc->best_nscore,
+                                     sc->early, isnew, cnt == 0, negs);
   double best_solution = sc->best_solution;
-  if (improved) {
-    best_score = score;
-    best_nscore = nscore;
-    best_solution = score - sc->lbabs;  // calculate_cut(best_spins), exact for integer weights
+  if (o.improved) {
+    best_solution = cut_solution(score, sc->lbabs);
 #pragma unroll
     for (int k = 0; k < VPT; ++k) bs[k] = s[k];
   }
   int ham = 0;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) ham += __popcll(__ballot(bs[k] != s[k]));
-  // termination (:541-556)
-  bool done = (t == T);
-  if (a.cfg.stopping == ECO_STOP_EARLY && early == 15) done = true;
-  if (a.cfg.stopping == ECO_STOP_QUARTER && t == T / 4) done = true;
-  if (!a.cfg.reversible_spins && negs == 0) done = true;
   // write back
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
     if (v < N) {
-      gsp[v] = (int8_t)s[k];
-      gh[v] = h[k];
-      gt[v] = (int16_t)tsf[k];
-      if (improved) gb[v] = (int8_t)bs[k];
+      rows.spins[v] = (int8_t)s[k];
+      rows.field[v] = h[k];
+      rows.tsf[v] = (int16_t)tsf[k];
+      if (o.improved) rows.best[v] = (int8_t)bs[k];
     }
   }
   if (lane == 0) {
     sc->score = score; sc->nscore = nscore;
-    sc->best_score = best_score; sc->best_nscore = best_nscore; sc->best_solution = best_solution;
-    sc->t = t; sc->hamming = ham; sc->done = done ? 1 : 0; sc->early = early;
-    a.rewards[e] = rew;
-    a.dones[e] = done ? 1 : 0;
+    sc->best_score = o.best_score; sc->best_nscore = o.best_nscore; sc->best_solution = best_solution;
+    sc->t = t; sc->hamming = ham; sc->done = o.done ? 1 : 0; sc->early = o.early;
+    a.rewards[e] = o.rew;
+    a.dones[e] = o.done ? 1 : 0;
   }
   ECO_ENV_TS(4);
   ObsCtx c;
   c.mlr = mlr;
-  const double dsc = score - best_score;
-  c.dist_best = (dsc < 0.0 ? -dsc : dsc) / mlr;                       // :516-519
+  c.dist_best = distance_from_best(score, o.best_score, mlr);
   c.hamming = (double)ham;                                            // :526-527
   c.nqi = (double)cnt / (double)N;                                    // :513-514
-  const double x = (double)(t - T) / (double)a.cfg.horizon_length + 1.0;
-  c.term = x > 0.0 ? x : 0.0;                                         // :509-511
+  c.term = termination_immanency(a.cfg, t);
   c.ep_time = tab_ptr(a)[t];                                          // :506
   c.basis = a.cfg.spin_basis;
-  if (FASTOBS) write_obs_default<VPT, F>(a, e, lane, s, h, tsf, c);
-  else write_obs<VPT, F>(a, e, lane, s, h, tsf, c);
+  if (FASTOBS) write_obs_default<VPT, 64, F, !FW>(a, e, lane, s, h, tsf, c);
+  else write_obs<VPT, 64, F>(a, e, lane, s, h, tsf, c);
   ECO_ENV_TS(5);
 }
 template <int VPT, bool FASTOBS, class F = int>
@@ -564,36 +458,18 @@ __global__ __launch_bounds__(256) void env_greedy_kernel(EnvArgs a, int32_t* act
     if (lane == 0) actions[e] = 0;
     return;
   }
-  const int8_t* gsp = (const int8_t*)(a.state + a.L.off_spins) + (size_t)e * N;
-  const F* gh = (const F*)(a.state + a.L.off_field) + (size_t)e * N;
-  F best;
-  if constexpr (std::is_same_v<F, double>) best = -INFINITY; else best = INT_MIN;
-  int bi = 0x7fffffff;
+  const EpRows<F> rows(a, e);
+  GreedyArgmax<F> m;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
     if (v < N) {
-      const int s = gsp[v];
-      if (a.cfg.reversible_spins || s < 0) {
-        const F g = s * gh[v];
-        if (g > best || (g == best && v < bi)) { best = g; bi = v; }
-      }
+      const int s = rows.spins[v];
+      if (a.cfg.reversible_spins || s < 0) m.offer(s * rows.field[v], v);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const F ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if (lane == 0) {
-    if (best < 0 || bi == 0x7fffffff) {  // no improving (or no allowed) flip: solver stops
-      sc->done = 1;
-      actions[e] = 0;
-    } else {
-      actions[e] = bi;
-    }
-  }
+  m.wave_reduce();
+  if (lane == 0) m.finish(sc, actions, e);
 }
 
 // read-out of episode scalars / spins

@@ -62,25 +62,10 @@ template <int VPT>
 __device__ __forceinline__ void write_prob_obs(const EnvArgs& a, int e, int lane, const int (&s)[VPT],
                                                const int (&qm)[VPT], const int (&im)[VPT], const int (&vm)[VPT],
                                                const int (&tsf)[VPT], const ProbObs& c, bool cut_like) {
-  const int N = a.cfg.n_spins;
-  const int nobs = a.cfg.n_obs;
   const double* tab = tab_ptr(a);
-#pragma unroll
-  for (int k = 0; k < VPT; ++k) {
-    const int v = lane + 64 * k;
-    if (v >= N) continue;
-    float xf[ECO_MAX_OBS];
-#pragma unroll
-    for (int i = 0; i < ECO_MAX_OBS; ++i) {
-      double val = 0.0;
-      if (i < nobs) {
-        val = prob_obs_value(a.cfg.obs_ids[i], c, s[k], qm[k], im[k], vm[k], tsf[k], tab, cut_like);
-        if (a.obs_f64) a.obs_f64[((size_t)e * nobs + i) * N + v] = val;
-      }
-      xf[i] = (float)val;
-    }
-    if (a.obs_x) store_obs_row(a.obs_x, (size_t)e * N + v, nobs, xf);
-  }
+  write_obs_rows<VPT, 64>(a, e, lane, [&](int k, int id) {
+    return prob_obs_value(id, c, s[k], qm[k], im[k], vm[k], tsf[k], tab, cut_like);
+  });
 }
 
 // SpinSystemBase.reset (spinsystem.py:183-259) + _reset_state (:283-330) for the generic scorers.
@@ -110,14 +95,7 @@ __global__ __launch_bounds__(256) void env_reset_problem_kernel(EnvArgs a) {
     const int v = lane + 64 * k;
     int sv = 0;
     if (v < N) {
-      if (a.spins_in) {
-        sv = a.spins_in[(size_t)e * N + v];
-        if (sv != 1 && sv != -1) { atomicCAS(a.err, 0, ECO_ERR_BASIS); sv = -1; }
-      } else if (a.cfg.reversible_spins) {
-        sv = (int)(rng3(a.seed, (uint64_t)e, (uint64_t)v) >> 63) * 2 - 1;
-      } else {
-        sv = -1;
-      }
+      sv = initial_spin(a, e, v);
       my_s[v] = (int8_t)sv;
     }
     s[k] = sv;
@@ -235,27 +213,18 @@ __global__ __launch_bounds__(256) void env_reset_problem_kernel(EnvArgs a) {
     const bool valid = inv == 0;
     score = (double)(valid ? q : 0) - (double)inv;
     nscore = (double)(valid ? q : 0) / qn - (double)inv / inorm;
-    solution = valid ? (double)n1 : (target_maximises(tgt) ? 0.0 : (double)N);
+    solution = set_solution(tgt, n1, valid, N);
   }
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gF = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<int32_t> rows(a, e);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    if (v < N) { gsp[v] = (int8_t)s[k]; gF[v] = F[k]; gt[v] = 0; gb[v] = (int8_t)s[k]; }
+    if (v < N) { rows.spins[v] = (int8_t)s[k]; rows.field[v] = F[k]; rows.tsf[v] = 0; rows.best[v] = (int8_t)s[k]; }
   }
   uint32_t* vidx = (uint32_t*)(a.state + L.off_vidx) + (size_t)e * L.cap;
   for (int i = lane; i < L.cap; i += 64) vidx[i] = 0u;
   if (lane == 0) {
-    sc->score = score; sc->nscore = nscore;
-    sc->best_score = score; sc->best_nscore = nscore; sc->best_solution = solution;
-    sc->mlr = mlr; sc->qn = qn; sc->lbabs = lb < 0.0 ? -lb : lb;
-    sc->hash = 0ull; sc->t = 0; sc->hamming = 0; sc->graph = gid; sc->done = 0; sc->early = 0;
-    sc->visit_count = 0;
-    sc->inorm = inorm; sc->lb = lb;
-    sc->n1 = n1; sc->inv = inv; sc->best_n1 = n1; sc->best_inv = inv;
+    store_reset_scalars(sc, score, nscore, solution, mlr, qn, lb, inorm, gid, n1, inv);
     // the normaliser these reset rows are written with (the compact replay ring rebuilds them from it)
     ((double*)(a.state + L.off_oinorm))[e] = stale_inorm;
   }
@@ -305,10 +274,8 @@ __global__ __launch_bounds__(256) void env_step_problem_kernel(EnvArgs a) {
   const int e = uniform_i(blockIdx.x * 4 + wv);
   if (e >= a.B) return;
   const int N = a.cfg.n_spins;
-  const int T = a.cfg.max_steps;
   const int tgt = a.cfg.optimisation_target;
   const bool cut_like = tgt == ECO_TARGET_MIN_CUT;
-  const EnvLayout& L = a.L;
   uint8_t* c_lds = reinterpret_cast<uint8_t*>(d_lds + 4 * N);
   EpScal* sc = scal_ptr(a) + e;
   const int act = uniform_i(a.actions[e]);  // loaded alongside the done flag
@@ -321,10 +288,7 @@ __global__ __launch_bounds__(256) void env_step_problem_kernel(EnvArgs a) {
     return;
   }
   const int t = sc->t + 1;
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gF = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<int32_t> rows(a, e);
   const int gid = sc->graph;
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
@@ -332,7 +296,7 @@ __global__ __launch_bounds__(256) void env_step_problem_kernel(EnvArgs a) {
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    if (v < N) { s[k] = gsp[v]; F[k] = gF[v]; tsf[k] = gt[v]; bs[k] = gb[v]; }
+    if (v < N) { s[k] = rows.spins[v]; F[k] = rows.field[v]; tsf[k] = rows.tsf[v]; bs[k] = rows.best[v]; }
     else { s[k] = 0; F[k] = 0; tsf[k] = 0; bs[k] = 0; }
   }
   int sa_old, Fa;
@@ -346,7 +310,7 @@ __global__ __launch_bounds__(256) void env_step_problem_kernel(EnvArgs a) {
       const uint32_t x = ed[q];
       if (edge_w(x) > 0) {
         const int k = edge_col(x);
-        const uint8_t c = mds_code(gsp[k], gF[k]);
+        const uint8_t c = mds_code(rows.spins[k], rows.field[k]);
         S0a += c & 1;
         S1a += c >> 1;
       }
@@ -404,70 +368,47 @@ __global__ __launch_bounds__(256) void env_step_problem_kernel(EnvArgs a) {
   }
   const bool isnew = (a.cfg.has_basin_reward || a.cfg.has_stag_punishment) ? history_update<VPT>(a, e, lane, sc, act, words)
                                                                             : true;
-  // reward (:418-457)
-  double best_score = sc->best_score, best_nscore = sc->best_nscore;
-  double rew = 0.0;
-  int early = sc->early + 1;
-  const bool improved = score > best_score;
-  if (improved) {
-    early = 0;
-    if (a.cfg.reward_signal == ECO_REWARD_BLS) rew = a.cfg.norm_rewards ? nscore - best_nscore : score - best_score;
-  }
-  if (a.cfg.reward_signal == ECO_REWARD_DENSE) rew = a.cfg.norm_rewards ? fd.dn : fd.d;
-  if (a.cfg.has_stag_punishment && !isnew) rew -= a.cfg.stag_punishment;
-  if (a.cfg.has_basin_reward && all_le0 && isnew) rew += a.cfg.basin_reward;
-  // best tracking (:459-477)
+  // reward, best tracking, termination (:418-477, :541-556)
+  const StepOutcome o = step_outcome(a.cfg, t, score, nscore, fd.d, fd.dn, sc->best_score, sc->best_nscore, sc->early,
+                                     isnew, all_le0, negs);
   double best_solution = sc->best_solution;
   int best_n1 = sc->best_n1, best_inv = sc->best_inv;
-  if (improved) {
-    best_score = score;
-    best_nscore = nscore;
+  if (o.improved) {
     best_n1 = n1;
     best_inv = inv;
-    if (cut_like) best_solution = qn - score;  // cut(best) = max(0, qn) - quality, exact
-    else best_solution = valid ? (double)n1 : (target_maximises(tgt) ? 0.0 : (double)N);
+    best_solution = solution_of(tgt, score, 0.0, qn, n1, valid, N);  // |lb| is CUT's alone, and CUT never runs here
 #pragma unroll
     for (int k = 0; k < VPT; ++k) bs[k] = s[k];
   }
   int ham = 0;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) ham += __popcll(__ballot(bs[k] != s[k]));
-  bool done = (t == T);
-  if (a.cfg.stopping == ECO_STOP_EARLY && early == 15) done = true;
-  if (a.cfg.stopping == ECO_STOP_QUARTER && t == T / 4) done = true;
-  if (!a.cfg.reversible_spins && negs == 0) done = true;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
     if (v < N) {
-      gsp[v] = (int8_t)s[k];
-      gF[v] = F[k];
-      gt[v] = (int16_t)tsf[k];
-      if (improved) gb[v] = (int8_t)bs[k];
+      rows.spins[v] = (int8_t)s[k];
+      rows.field[v] = F[k];
+      rows.tsf[v] = (int16_t)tsf[k];
+      if (o.improved) rows.best[v] = (int8_t)bs[k];
     }
   }
   if (lane == 0) {
     sc->score = score; sc->nscore = nscore;
-    sc->best_score = best_score; sc->best_nscore = best_nscore; sc->best_solution = best_solution;
-    sc->t = t; sc->hamming = ham; sc->done = done ? 1 : 0; sc->early = early;
+    sc->best_score = o.best_score; sc->best_nscore = o.best_nscore; sc->best_solution = best_solution;
+    sc->t = t; sc->hamming = ham; sc->done = o.done ? 1 : 0; sc->early = o.early;
     sc->n1 = n1; sc->inv = inv; sc->best_n1 = best_n1; sc->best_inv = best_inv;
-    a.rewards[e] = rew;
-    a.dones[e] = done ? 1 : 0;
+    a.rewards[e] = o.rew;
+    a.dones[e] = o.done ? 1 : 0;
   }
   ProbObs c;
   c.mlr = mlr; c.inorm = inorm;
-  if (cut_like) {
-    const double dsc = score - best_score;
-    c.dist_best = (dsc < 0.0 ? -dsc : dsc) / mlr;
-  } else {
-    const int dq = set_quality(tgt, n1, N) - set_quality(tgt, best_n1, N);
-    c.dist_best = (double)(dq < 0 ? -dq : dq) / mlr;                      // :516-519
-  }
+  c.dist_best = cut_like ? distance_from_best(score, o.best_score, mlr)
+                         : set_distance_from_best(tgt, n1, best_n1, N, mlr);
   c.hamming = (double)ham;
   c.nqi = (double)nqi / (double)N;
   c.nvi = (double)nvi / (double)N;
-  const double xt = (double)(t - T) / (double)a.cfg.horizon_length + 1.0;
-  c.term = xt > 0.0 ? xt : 0.0;
+  c.term = termination_immanency(a.cfg, t);
   c.ep_time = tab_ptr(a)[t];
   c.gvd = (double)(inv - best_inv) / inorm;                                // :529-532
   c.valid = valid ? 1.0 : 0.0;
@@ -491,14 +432,13 @@ __global__ __launch_bounds__(256) void env_greedy_problem_kernel(EnvArgs a, int3
     if (lane == 0) actions[e] = 0;
     return;
   }
-  const int8_t* gsp = (const int8_t*)(a.state + a.L.off_spins) + (size_t)e * N;
-  const int32_t* gF = (const int32_t*)(a.state + a.L.off_field) + (size_t)e * N;
+  const EpRows<int32_t> rows(a, e);
   int s[VPT], F[VPT], S0[VPT], S1[VPT];
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
-    s[k] = v < N ? gsp[v] : 0;
-    F[k] = v < N ? gF[v] : 0;
+    s[k] = v < N ? rows.spins[v] : 0;
+    F[k] = v < N ? rows.field[v] : 0;
     S0[k] = 0; S1[k] = 0;
   }
   if (tgt == ECO_TARGET_MIN_DOM_SET) {
@@ -517,7 +457,7 @@ __global__ __launch_bounds__(256) void env_greedy_problem_kernel(EnvArgs a, int3
   const int n1 = sc->n1, inv = sc->inv;
   const int q = cut_like ? 0 : set_quality(tgt, n1, N);
   const int score = ((inv == 0) ? q : 0) - inv;
-  int best = INT_MIN, bi = 0x7fffffff;
+  GreedyArgmax<int> m;
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = lane + 64 * k;
@@ -525,23 +465,11 @@ __global__ __launch_bounds__(256) void env_greedy_problem_kernel(EnvArgs a, int3
       int qm, im;
       vertex_masks(tgt, s[k], F[k], n1, S0[k], S1[k], qm, im);
       const int ui = inv + im;
-      const int sm = cut_like ? qm : (ui == 0 ? q + qm : 0) - ui - score;
-      if (sm > best || (sm == best && v < bi)) { best = sm; bi = v; }
+      m.offer(cut_like ? qm : (ui == 0 ? q + qm : 0) - ui - score, v);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int ob = __shfl_xor(best, o, 64), oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if (lane == 0) {
-    if (best < 0 || bi == 0x7fffffff) {
-      sc->done = 1;
-      actions[e] = 0;
-    } else {
-      actions[e] = bi;
-    }
-  }
+  m.wave_reduce();
+  if (lane == 0) m.finish(sc, actions, e);
 }
 
 int env_reset_problem_launch(const EnvArgs& a, int blocks, size_t lds, hipStream_t st) {

@@ -7,31 +7,17 @@
 // for the workgroup-per-episode env above ECO_MAX_SPINS, which is CUT with integer weights).  The kernel only
 // reads the env state: the row's values are those the step kernels already keep --
 //   solution    the value the step kernels store as best_solution when a state becomes the best one
-//               (CUT: score - |lb|, MIN_CUT: qn - score, set problems: n1 if valid, else N / 0);
+//               (solution_of: CUT score - |lb|, MIN_CUT qn - score, set problems n1 if valid, else N / 0);
 //   valid       inv == 0 (cut targets: always);
 //   score_mask  every vertex's score change, from the resident neighbour sums with the arithmetic the greedy
 //               kernels rank by (eco_env.hip env_greedy_kernel, eco_env_problems.hip
-//               env_greedy_problem_kernel) -- for ALL vertices: the reference records the unmasked
+//               env_greedy_problem_kernel; the masks are vertex_masks, mds_code and set_quality of
+//               eco_env_dev.h, as there) -- for ALL vertices: the reference records the unmasked
 //               scorer.get_score_mask, also in irreversible envs.
 // No atomics, no host read; every destination is optional (NULL = not recorded).
 #include "eco_env_dev.h"
 
 namespace eco {
-
-// eco_env_problems.hip's per-vertex masks, restated for the recorder (that translation unit keeps them
-// internal; tests/test_env_record_gpu.py pins both to the same oracle)
-__device__ __forceinline__ void rec_vertex_masks(int t, int s, int F, int n1, int S0, int S1, int& qm, int& im) {
-  switch (t) {
-    case ECO_TARGET_MIN_COVER: qm = s; im = s * F; break;
-    case ECO_TARGET_MAX_IND_SET: qm = -s; im = -s * F; break;
-    case ECO_TARGET_MAX_CLIQUE: qm = -s; im = s > 0 ? 2 * (F - n1 + 1) : 2 * (n1 - F); break;
-    default: {  // MIN_DOM_SET
-      const int alone = F == 0;
-      qm = s; im = s > 0 ? alone + S1 : -alone - S0;
-      break;
-    }
-  }
-}
 
 struct RecordArgs {
   eco_env_history h;
@@ -54,8 +40,7 @@ __global__ __launch_bounds__(256) void env_record_kernel(EnvArgs a, RecordArgs r
   const int B = a.B;
   const int tgt = a.cfg.optimisation_target;
   const EpScal* sc = scal_ptr(a) + e;
-  const int8_t* gsp = (const int8_t*)(a.state + a.L.off_spins) + (size_t)e * N;
-  const F* gF = (const F*)(a.state + a.L.off_field) + (size_t)e * N;
+  const EpRows<F> rows(a, e);
   const size_t re = (size_t)r.row * B + e;  // [rows][B]
   const size_t rv = re * N;                 // [rows][B][N]
   const bool cut_like = tgt == ECO_TARGET_CUT || tgt == ECO_TARGET_MIN_CUT;
@@ -64,13 +49,7 @@ __global__ __launch_bounds__(256) void env_record_kernel(EnvArgs a, RecordArgs r
   if (lane == 0) {
     if (r.h.action) r.h.action[re] = (r.row > 0 && r.actions) ? (double)r.actions[e] : 0.0;
     if (r.h.reward) r.h.reward[re] = (r.row > 0 && r.rewards) ? r.rewards[e] : 0.0;
-    if (r.h.solution) {
-      double sol;
-      if (tgt == ECO_TARGET_CUT) sol = sc->score - sc->lbabs;
-      else if (tgt == ECO_TARGET_MIN_CUT) sol = sc->qn - sc->score;
-      else sol = valid ? (double)n1 : ((tgt == ECO_TARGET_MAX_IND_SET || tgt == ECO_TARGET_MAX_CLIQUE) ? 0.0 : (double)N);
-      r.h.solution[re] = sol;
-    }
+    if (r.h.solution) r.h.solution[re] = solution_of(tgt, sc->score, sc->lbabs, sc->qn, n1, valid, N);
     if (r.h.score) r.h.score[re] = sc->score;
     if (r.h.valid) r.h.valid[re] = valid ? 1 : 0;
     if (r.h.length) r.h.length[e] = r.row + 1;
@@ -80,16 +59,16 @@ __global__ __launch_bounds__(256) void env_record_kernel(EnvArgs a, RecordArgs r
     for (int v = lane; v < N; v += 64) r.h.qs[rv + v] = have ? r.q[(size_t)e * N + v] : 0.f;
   }
   if (r.h.spins)
-    for (int v = lane; v < N; v += 64) r.h.spins[rv + v] = gsp[v];
+    for (int v = lane; v < N; v += 64) r.h.spins[rv + v] = rows.spins[v];
   if (!r.h.score_mask) return;
   double* sm_out = r.h.score_mask + rv;
   if constexpr (std::is_same_v<F, double>) {  // float-weighted CUT: s * (J s) in float64
-    for (int v = lane; v < N; v += 64) sm_out[v] = (double)gsp[v] * gF[v];
+    for (int v = lane; v < N; v += 64) sm_out[v] = (double)rows.spins[v] * rows.field[v];
     return;
   } else {
     if (cut_like) {  // calculate_cut_changes: the f64 product s * (J s) (keeps -0.0), negated for MIN_CUT
       for (int v = lane; v < N; v += 64) {
-        const double g = (double)gsp[v] * (double)gF[v];
+        const double g = (double)rows.spins[v] * (double)rows.field[v];
         sm_out[v] = tgt == ECO_TARGET_CUT ? g : -g;
       }
       return;
@@ -98,21 +77,17 @@ __global__ __launch_bounds__(256) void env_record_kernel(EnvArgs a, RecordArgs r
     uint8_t* code = rc_lds + (size_t)wv * N;
     const int32_t* rp = nullptr;
     const uint32_t* ed = nullptr;
-    if (mds) {  // codes of the whole episode: bit0 = (x = 0, P = 0), bit1 = (x = 0, P = 1)
+    if (mds) {  // codes of the whole episode
       const int gid = sc->graph;
       rp = a.gs.row_ptr + (size_t)gid * (N + 1);
       ed = a.gs.edges + a.gs.edge_base[gid];
-      for (int v = lane; v < N; v += 64) {
-        const int s = gsp[v], P = gF[v];
-        code[v] = s < 0 ? (uint8_t)((P == 0) | ((P == 1) << 1)) : (uint8_t)0;
-      }
+      for (int v = lane; v < N; v += 64) code[v] = mds_code(rows.spins[v], rows.field[v]);
       wave_lds_sync();
     }
-    const bool maxi = tgt == ECO_TARGET_MAX_IND_SET || tgt == ECO_TARGET_MAX_CLIQUE;
-    const int q = maxi ? n1 : N - n1;             // solution quality of the current set
+    const int q = set_quality(tgt, n1, N);        // solution quality of the current set
     const int score = (inv == 0 ? q : 0) - inv;   // scorer.get_score (integer-valued)
     for (int v = lane; v < N; v += 64) {
-      const int s = gsp[v], Fv = gF[v];
+      const int s = rows.spins[v], Fv = rows.field[v];
       int S0 = 0, S1 = 0;
       if (mds) {
         const int q1 = rp[v + 1];
@@ -125,7 +100,7 @@ __global__ __launch_bounds__(256) void env_record_kernel(EnvArgs a, RecordArgs r
         }
       }
       int qm, im;
-      rec_vertex_masks(tgt, s, Fv, n1, S0, S1, qm, im);
+      vertex_masks(tgt, s, Fv, n1, S0, S1, qm, im);
       const int ui = inv + im;
       sm_out[v] = (double)((ui == 0 ? q + qm : 0) - ui - score);  // score_solver.py:310-324
     }

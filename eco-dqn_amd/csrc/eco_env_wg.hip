@@ -14,8 +14,9 @@
 // N = 8192) and the owning threads add them.  OptimisationTarget.CUT with integer weights only (the host
 // rejects float-weighted sets and the generic-scorer targets above ECO_MAX_SPINS); both spin bases, reversible and
 // irreversible spins, every Stopping mode, the DEFAULT_OBSERVABLES fast write and the general observable write.
-// Semantics: spinsystem.py:183-259, :283-330 (reset) and :355-559 (step), stated operation for operation as in
-// eco_env.hip.  No atomics beyond the error word's atomicCAS the existing kernels use.
+// Semantics: spinsystem.py:183-259, :283-330 (reset) and :355-559 (step); the episode logic (initial spin, reward,
+// stopping, observation rows, the greedy compare) is the one copy of eco_env_dev.h that eco_env.hip calls too.  No
+// atomics beyond the error word's atomicCAS the existing kernels use.
 //
 // Budget of env_step_wg_kernel<32> (N = 8192): dynamic LDS 4 N = 32 KB + 80 B static; per thread 32 slots x
 // {s, h, tsf, best} = 128 VGPRs of state, the slot's g and the 64-bit ballots are transient (the build reports
@@ -29,54 +30,6 @@ namespace {
 
 constexpr int WG_NT = 256;  // threads per episode
 constexpr int WG_NW = 4;    // waves per episode
-
-// Observation rows of the episode (write_obs / write_obs_default of eco_env.hip with v = tid + 256 k).
-template <int VPT>
-__device__ __forceinline__ void wg_write_obs(const EnvArgs& a, int e, int tid, const int (&s)[VPT], const int (&h)[VPT],
-                                             const int (&tsf)[VPT], const ObsCtx& c) {
-  const int N = a.cfg.n_spins;
-  const int nobs = a.cfg.n_obs;
-  const double* tab = tab_ptr(a);
-#pragma unroll
-  for (int k = 0; k < VPT; ++k) {
-    const int v = tid + WG_NT * k;
-    if (v >= N) continue;
-    float xf[ECO_MAX_OBS];
-#pragma unroll
-    for (int i = 0; i < ECO_MAX_OBS; ++i) {
-      double val = 0.0;
-      if (i < nobs) {
-        val = obs_value(a.cfg.obs_ids[i], c, s[k], h[k], tsf[k], tab);
-        if (a.obs_f64) a.obs_f64[((size_t)e * nobs + i) * N + v] = val;
-      }
-      xf[i] = (float)val;
-    }
-    if (a.obs_x) store_obs_row(a.obs_x, (size_t)e * N + v, nobs, xf);
-  }
-}
-
-// DEFAULT_OBSERVABLES, fp32 rows only: the three per-vertex values and the four block-uniform ones, converted once.
-// g / mlr is the reference's f64 quotient rounded to f32, as the general write does: the f32 division of
-// eco_env.hip's write_obs_default needs |g|, mlr < 2^18, which 8191 neighbours of weight 127 exceed.
-template <int VPT>
-__device__ __forceinline__ void wg_write_obs_default(const EnvArgs& a, int e, int tid, const int (&s)[VPT],
-                                                     const int (&h)[VPT], const int (&tsf)[VPT], const ObsCtx& c) {
-  const int N = a.cfg.n_spins;
-  const double* tab = tab_ptr(a);
-  const float u3 = (float)c.dist_best, u4 = (float)c.hamming, u5 = (float)c.nqi, u6 = (float)c.term;
-  const bool binary = c.basis == ECO_BASIS_BINARY;
-#pragma unroll
-  for (int k = 0; k < VPT; ++k) {
-    const int v = tid + WG_NT * k;
-    if (v >= N) continue;
-    const float x0 = binary ? (float)((1 - s[k]) / 2) : (float)s[k];
-    const float x1 = (float)(((double)s[k] * (double)h[k]) / c.mlr);  // keeps -0.0
-    const float x2 = (float)tab[tsf[k]];
-    float4* dst = (float4*)(a.obs_x + ((size_t)e * N + v) * 8);
-    dst[0] = make_float4(x0, x1, x2, u3);
-    dst[1] = make_float4(u4, u5, u6, 0.f);
-  }
-}
 
 // SpinSystemBase.reset (spinsystem.py:183-259) + _reset_state (:283-330); one workgroup per episode.
 template <int VPT>
@@ -106,14 +59,7 @@ __global__ __launch_bounds__(WG_NT) void env_reset_wg_kernel(EnvArgs a) {
     const int v = tid + WG_NT * k;
     int sv = 0;
     if (v < N) {
-      if (a.spins_in) {
-        sv = a.spins_in[(size_t)e * N + v];
-        if (sv != 1 && sv != -1) { atomicCAS(a.err, 0, ECO_ERR_BASIS); sv = -1; }
-      } else if (a.cfg.reversible_spins) {
-        sv = (int)(rng3(a.seed, (uint64_t)e, (uint64_t)v) >> 63) * 2 - 1;  // 2*randint(2)-1
-      } else {
-        sv = -1;  // irreversible: all -1 (spinsystem.py:295-297)
-      }
+      sv = initial_spin(a, e, v);
       s_lds[v] = (int8_t)sv;
     }
     s[k] = sv;
@@ -155,31 +101,19 @@ __global__ __launch_bounds__(WG_NT) void env_reset_wg_kernel(EnvArgs a) {
   const double lbabs = lb < 0.0 ? -lb : lb;
   const double score = cut + lbabs;   // MaximizationProblem.get_score (score_solver.py:182-188)
   const double nscore = score / qn;   // get_normalized_score (:190-194)
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gh = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<int32_t> rows(a, e);
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = tid + WG_NT * k;
-    if (v < N) { gsp[v] = (int8_t)s[k]; gh[v] = h[k]; gt[v] = 0; gb[v] = (int8_t)s[k]; }
+    if (v < N) { rows.spins[v] = (int8_t)s[k]; rows.field[v] = h[k]; rows.tsf[v] = 0; rows.best[v] = (int8_t)s[k]; }
   }
   uint32_t* vidx = (uint32_t*)(a.state + L.off_vidx) + (size_t)e * L.cap;
   for (int i = tid; i < L.cap; i += WG_NT) vidx[i] = 0u;
-  if (tid == 0) {
-    EpScal* sc = scal_ptr(a) + e;
-    sc->score = score; sc->nscore = nscore;
-    sc->best_score = score; sc->best_nscore = nscore; sc->best_solution = cut;
-    sc->mlr = mlr; sc->qn = qn; sc->lbabs = lbabs;
-    sc->hash = 0ull; sc->t = 0; sc->hamming = 0; sc->graph = gid; sc->done = 0; sc->early = 0;
-    sc->visit_count = 0;
-    sc->inorm = 1.0; sc->lb = lb; sc->inv = 0; sc->best_inv = 0;
-    sc->n1 = n1; sc->best_n1 = n1;
-  }
+  if (tid == 0) store_reset_scalars(scal_ptr(a) + e, score, nscore, cut, mlr, qn, lb, 1.0, gid, n1, 0);
   ObsCtx c;
   c.mlr = mlr; c.dist_best = 0.0; c.hamming = 0.0; c.nqi = (double)cnt / (double)N;
   c.term = 0.0; c.ep_time = 0.0; c.basis = a.cfg.spin_basis;
-  wg_write_obs<VPT>(a, e, tid, s, h, tsf, c);
+  write_obs<VPT, WG_NT, int>(a, e, tid, s, h, tsf, c);
 }
 
 // SpinSystemBase.step (spinsystem.py:355-559), ExtraAction.NONE, memory_length None; one workgroup per episode.
@@ -213,31 +147,30 @@ __global__ __launch_bounds__(WG_NT) void env_step_wg_kernel(EnvArgs a) {
   const int t = sc->t + 1;  // :362
   const double qn = sc->qn, mlr = sc->mlr, lbabs = sc->lbabs;
   const double score0 = sc->score, nscore0 = sc->nscore;
-  double best_score = sc->best_score, best_nscore = sc->best_nscore, best_solution = sc->best_solution;
+  const double best_score = sc->best_score, best_nscore = sc->best_nscore;
+  double best_solution = sc->best_solution;
   const uint64_t hash0 = sc->hash;
   const int early0 = sc->early, visits0 = sc->visit_count;
   const int gid = sc->graph;
-  int8_t* gsp = (int8_t*)(a.state + L.off_spins) + (size_t)e * N;
-  int32_t* gh = (int32_t*)(a.state + L.off_field) + (size_t)e * N;
-  int16_t* gt = (int16_t*)(a.state + L.off_tsf) + (size_t)e * N;
-  int8_t* gb = (int8_t*)(a.state + L.off_best) + (size_t)e * N;
+  const EpRows<int32_t> rows(a, e);
   const int32_t* rp = a.gs.row_ptr + (size_t)gid * (N + 1);
   const uint32_t* ed = a.gs.edges + a.gs.edge_base[gid];
   const int q0 = rp[act], q1 = rp[act + 1];
-  const int sa_old = gsp[act];  // pre-flip spin and field of the flipped vertex (one broadcast load each)
-  const int ha = gh[act];
+  const int sa_old = rows.spins[act];  // pre-flip spin and field of the flipped vertex (one broadcast load each)
+  const int ha = rows.field[act];
   int s[VPT], tsf[VPT], bs[VPT], h[VPT];
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = tid + WG_NT * k;
-    if (v < N) { s[k] = gsp[v]; h[k] = gh[v]; tsf[k] = gt[v]; bs[k] = gb[v]; d_lds[v] = 0; }
+    if (v < N) { s[k] = rows.spins[v]; h[k] = rows.field[v]; tsf[k] = rows.tsf[v]; bs[k] = rows.best[v]; d_lds[v] = 0; }
     else { s[k] = 0; h[k] = 0; tsf[k] = 0; bs[k] = 0; }
   }
   const double delta = (double)sa_old * (double)ha;  // f64 product: keeps -0.0 like the reference
   const double delta_n = delta / qn;                 // get_normalized_score_mask(state)[action] (:394)
   const double score = score0 + delta;               // :399
   const double nscore = nscore0 + delta_n;           // :400 (accumulated)
-  const bool improved = score > best_score;
+  // step_outcome's `improved`, for the best-spins update inside the reduction loop only; after the call o.improved
+  const bool improved_early = score > best_score;
   // incremental local field: h_j -= 2 w_aj s_a(old) over the CSR row of `act` (distinct columns: no collisions)
   __syncthreads();  // d zeroed; every load of the old state and scalars above has completed
   for (int q = q0 + tid; q < q1; q += WG_NT) {
@@ -259,7 +192,7 @@ __global__ __launch_bounds__(WG_NT) void env_step_wg_kernel(EnvArgs a) {
     cnt += __popcll(__ballot(g > 0));
     words[k] = __ballot(s[k] > 0);
     negs += __popcll(__ballot(s[k] < 0));
-    if (improved) bs[k] = s[k];
+    if (improved_early) bs[k] = s[k];
     ham += __popcll(__ballot(bs[k] != s[k]));
   }
   if (lane == 0) { r_cnt[wv] = cnt; r_neg[wv] = negs; r_ham[wv] = ham; }
@@ -307,42 +240,25 @@ __global__ __launch_bounds__(WG_NT) void env_step_wg_kernel(EnvArgs a) {
       if (wi < W) vst[(size_t)visits0 * W + wi] = words[k];
     }
   }
-  // reward (:418-457)
-  double rew = 0.0;
-  int early = early0 + 1;
-  if (improved) {
-    early = 0;
-    if (a.cfg.reward_signal == ECO_REWARD_BLS)
-      rew = a.cfg.norm_rewards ? nscore - best_nscore : score - best_score;
-  }
-  if (a.cfg.reward_signal == ECO_REWARD_DENSE) rew = a.cfg.norm_rewards ? delta_n : delta;
-  if (a.cfg.has_stag_punishment && !isnew) rew -= a.cfg.stag_punishment;
-  if (a.cfg.has_basin_reward && cnt == 0 && isnew) rew += a.cfg.basin_reward;
-  if (improved) {
-    best_score = score;
-    best_nscore = nscore;
-    best_solution = score - lbabs;  // calculate_cut(best_spins), exact for integer weights
-  }
-  // termination (:541-556)
-  bool done = (t == T);
-  if (a.cfg.stopping == ECO_STOP_EARLY && early == 15) done = true;
-  if (a.cfg.stopping == ECO_STOP_QUARTER && t == T / 4) done = true;
-  if (!a.cfg.reversible_spins && negs == 0) done = true;
+  // reward, best tracking, termination (:418-477, :541-556)
+  const StepOutcome o = step_outcome(a.cfg, t, score, nscore, delta, delta_n, best_score, best_nscore, early0, isnew,
+                                     cnt == 0, negs);
+  if (o.improved) best_solution = cut_solution(score, lbabs);
   // write back
 #pragma unroll
   for (int k = 0; k < VPT; ++k) {
     const int v = tid + WG_NT * k;
     if (v < N) {
-      gsp[v] = (int8_t)s[k];
-      gh[v] = h[k];
-      gt[v] = (int16_t)tsf[k];
-      if (improved) gb[v] = (int8_t)bs[k];
+      rows.spins[v] = (int8_t)s[k];
+      rows.field[v] = h[k];
+      rows.tsf[v] = (int16_t)tsf[k];
+      if (o.improved) rows.best[v] = (int8_t)bs[k];
     }
   }
   if (tid == 0) {
     sc->score = score; sc->nscore = nscore;
-    sc->best_score = best_score; sc->best_nscore = best_nscore; sc->best_solution = best_solution;
-    sc->t = t; sc->hamming = ham; sc->done = done ? 1 : 0; sc->early = early;
+    sc->best_score = o.best_score; sc->best_nscore = o.best_nscore; sc->best_solution = best_solution;
+    sc->t = t; sc->hamming = ham; sc->done = o.done ? 1 : 0; sc->early = o.early;
     if (track) {
       sc->hash = hash;
       if (isnew) {
@@ -351,21 +267,19 @@ __global__ __launch_bounds__(WG_NT) void env_step_wg_kernel(EnvArgs a) {
         sc->visit_count = visits0 + 1;
       }
     }
-    a.rewards[e] = rew;
-    a.dones[e] = done ? 1 : 0;
+    a.rewards[e] = o.rew;
+    a.dones[e] = o.done ? 1 : 0;
   }
   ObsCtx c;
   c.mlr = mlr;
-  const double dsc = score - best_score;
-  c.dist_best = (dsc < 0.0 ? -dsc : dsc) / mlr;                       // :516-519
+  c.dist_best = distance_from_best(score, o.best_score, mlr);
   c.hamming = (double)ham;                                            // :526-527
   c.nqi = (double)cnt / (double)N;                                    // :513-514
-  const double x = (double)(t - T) / (double)a.cfg.horizon_length + 1.0;
-  c.term = x > 0.0 ? x : 0.0;                                         // :509-511
+  c.term = termination_immanency(a.cfg, t);
   c.ep_time = tab_ptr(a)[t];                                          // :506
   c.basis = a.cfg.spin_basis;
-  if (FASTOBS) wg_write_obs_default<VPT>(a, e, tid, s, h, tsf, c);
-  else wg_write_obs<VPT>(a, e, tid, s, h, tsf, c);
+  if (FASTOBS) write_obs_default<VPT, WG_NT, int, false>(a, e, tid, s, h, tsf, c);
+  else write_obs<VPT, WG_NT, int>(a, e, tid, s, h, tsf, c);
 }
 
 // Greedy solver action (src/agents/solver.py:100-131): first index of the largest g = s * (J s) over the allowed
@@ -384,34 +298,18 @@ __global__ __launch_bounds__(WG_NT) void env_greedy_wg_kernel(EnvArgs a, int32_t
     if (tid == 0) actions[e] = 0;
     return;
   }
-  const int8_t* gsp = (const int8_t*)(a.state + a.L.off_spins) + (size_t)e * N;
-  const int32_t* gh = (const int32_t*)(a.state + a.L.off_field) + (size_t)e * N;
-  int best = INT_MIN;
-  int bi = 0x7fffffff;
+  const EpRows<int32_t> rows(a, e);
+  GreedyArgmax<int> m;
   for (int v = tid; v < N; v += WG_NT) {  // ascending v: a later equal value never replaces an earlier one
-    const int s = gsp[v];
-    if (a.cfg.reversible_spins || s < 0) {
-      const int g = s * gh[v];
-      if (g > best || (g == best && v < bi)) { best = g; bi = v; }
-    }
+    const int s = rows.spins[v];
+    if (a.cfg.reversible_spins || s < 0) m.offer(s * rows.field[v], v);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if (lane == 0) { r_best[wv] = best; r_idx[wv] = bi; }
+  m.wave_reduce();
+  if (lane == 0) { r_best[wv] = m.best; r_idx[wv] = m.idx; }
   __syncthreads();
   if (tid == 0) {
-    for (int k = 1; k < WG_NW; ++k)
-      if (r_best[k] > best || (r_best[k] == best && r_idx[k] < bi)) { best = r_best[k]; bi = r_idx[k]; }
-    if (best < 0 || bi == 0x7fffffff) {  // no improving (or no allowed) flip: solver stops
-      sc->done = 1;
-      actions[e] = 0;
-    } else {
-      actions[e] = bi;
-    }
+    for (int k = 1; k < WG_NW; ++k) m.offer(r_best[k], r_idx[k]);
+    m.finish(sc, actions, e);
   }
 }
 

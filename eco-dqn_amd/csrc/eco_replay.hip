@@ -207,10 +207,8 @@ struct CutRing {
       const int t = sc->t;
       double dist = 0.0, term = 0.0;  // a reset state's rows are 0 (_reset_state never sets them)
       if (t > 0) {
-        const double dsc = sc->score - sc->best_score;
-        dist = (dsc < 0.0 ? -dsc : dsc) / sc->mlr;                          // spinsystem.py:516-519
-        const double x = (double)(t - cfg.max_steps) / (double)cfg.horizon_length + 1.0;
-        term = x > 0.0 ? x : 0.0;                                           // :509-511
+        dist = distance_from_best(sc->score, sc->best_score, sc->mlr);
+        term = termination_immanency(cfg, t);
       }
       const double v = threadIdx.x == 0 ? dist : threadIdx.x == 1 ? term : threadIdx.x == 2 ? (double)t
                                                                                             : (double)sc->hamming;
@@ -283,13 +281,8 @@ struct ProbRing {
       double dist = 0.0, gvd = 0.0, inorm = ((const double*)(state + L.off_oinorm))[e];
       if (t > 0) {  // env_step_problem_kernel's statements on the values it left in the record
         inorm = sc->inorm;
-        if (tgt == ECO_TARGET_MIN_CUT) {
-          const double dsc = sc->score - sc->best_score;
-          dist = (dsc < 0.0 ? -dsc : dsc) / sc->mlr;
-        } else {
-          const int dq = set_quality(tgt, sc->n1, N) - set_quality(tgt, sc->best_n1, N);
-          dist = (double)(dq < 0 ? -dq : dq) / sc->mlr;
-        }
+        dist = tgt == ECO_TARGET_MIN_CUT ? distance_from_best(sc->score, sc->best_score, sc->mlr)
+                                         : set_distance_from_best(tgt, sc->n1, sc->best_n1, N, sc->mlr);
         gvd = (double)(sc->inv - sc->best_inv) / inorm;
       }
       double v;
@@ -384,8 +377,7 @@ struct ProbRing {
     c.nvi = (double)nvi / (double)N;
     c.term = 0.0; c.ep_time = 0.0;
     if (t > 0) {
-      const double xt = (double)(t - cfg.max_steps) / (double)cfg.horizon_length + 1.0;
-      c.term = xt > 0.0 ? xt : 0.0;
+      c.term = termination_immanency(cfg, t);
       c.ep_time = tab[t];
     }
     c.valid = inv == 0 ? 1.0 : 0.0;
